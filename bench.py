@@ -10,12 +10,22 @@ One "step" = one CG iteration (src/conjugate_gradient.cpp:31-63): Ad = D D^dag d
 device, inputs resident in HBM. The CG runs with tol = 0 so every timed
 iteration does the full work.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the
+headline needs: set up the shard, the Dirac applies, W warmup and K timed CG
+iterations, the result line. `--full` adds the extras named below (the CPU
+baseline, the weak-scaling slab, the CG on the HMC-evolved field, at N > 1 the
+peer transport beside the headline); they take runs of their own after the
+headline's timing and appear as extra keys of the same line (null without
+`--full`). `--dump-outputs DIR` writes what the timed steps computed as .npy
+files (dump_outputs below); the inputs are counter-based and seeded, so two
+builds run with the same arguments can be compared output for output.
+
 Workloads (BASELINE.json configs):
   --config 3  (default for N = 1)  4096^2, beta=5 field, m0=-0.06, one GPU.
   --config 4  (default for N > 1)  the SAME 4096^2 lattice sharded along t over
               the N GPUs (strong scaling: N = 1 and N = 8 run one workload).
               The weak-scaling variant of config 4 (4096 x 512N, so N = 8 is
-              4096^2) is measured too and reported under "weak".
+              4096^2) is measured with --full and reported under "weak".
   --config 5  8192^2, beta=2 field (sigma 0.4242), m0=-0.19 (near m_crit),
               sharded over N GPUs: CG to 1e-10 from x0 = phi (the reference's
               start), time to solution, iterations and the true residual.
@@ -28,8 +38,8 @@ torch.distributed (gloo) is control plane only: the RCCL unique id / the peer
 regions' IPC handles, barriers and the max-over-ranks timing.
 
 Transports (N > 1): `--transport rccl` (the default, north_star's "RCCL halo
-exchange over xGMI") carries the headline `value`; the same run then times
-the device-initiated peer transport on the same workload as the extra key
+exchange over xGMI") carries the headline `value`; with --full the same run then
+times the device-initiated peer transport on the same workload as the extra key
 `peer_transport` (include/sm_hip.h sm_create_peer: kernels store faces and
 sums straight into the other GPUs' regions over xGMI; `--no-peer` skips it).
 Before timing the peer transport every rank checks it against the
@@ -87,8 +97,16 @@ def parse(argv=None):
                     help="BASELINE.json config (default: 3 on one GPU, 4 on several)")
     ap.add_argument("--nx", type=int, default=None, help="override the config's lattice (tests)")
     ap.add_argument("--nt", type=int, default=None)
-    ap.add_argument("--no-weak", action="store_true", help="skip the weak-scaling extra of config 3/4")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure the extras: the CPU baseline, the weak-scaling slab, "
+                         "the CG on the HMC-evolved field (N = 1) and the peer transport (N > 1); the --no-* "
+                         "options below drop single extras of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed (the CG's x after its last timed "
+                         "iteration, the last Dirac apply's output, the CG scalars) as DIR/<name>.npy, float64; "
+                         "fields above 2^21 values as a fixed seeded sample")
+    ap.add_argument("--no-weak", action="store_true", help="--full: skip the weak-scaling extra of config 3/4")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=None,
                     help="host cores for the CPU baseline (default: this process's CPU share)")
     ap.add_argument("--cpu-iters", type=int, default=50, help="CG iterations of the CPU baseline sample")
@@ -96,7 +114,7 @@ def parse(argv=None):
                     help="multi-GPU wire of the headline: RCCL, the device-initiated peer transport (checked "
                          "against the host-staged one first, RCCL if that fails), or the host-staged test transport")
     ap.add_argument("--no-peer", action="store_true",
-                    help="N > 1 with --transport rccl (or hosted): skip the extra timing of the peer transport")
+                    help="--full, N > 1 with --transport rccl (or hosted): skip the extra timing of the peer transport")
     ap.add_argument("--device", type=int, default=None, help="override the rank -> GPU mapping")
     ap.add_argument("--cg-path", choices=list(CG_PATH_ID), default="recompute")
     ap.add_argument("--rank-timeout", type=float, default=900.0,
@@ -106,7 +124,7 @@ def parse(argv=None):
                     help="recompute-Ad CG reads the complex links (160 B/site) instead of their exact "
                          "codes (145 or 148; the default from 4M sites per shard)")
     ap.add_argument("--evolved-trajectories", type=int, default=50,
-                    help="N = 1: also time the CG on the field after this many pure-gauge leapfrog "
+                    help="--full, N = 1: also time the CG on the field after this many pure-gauge leapfrog "
                          "trajectories (the HMC's link update; 0 skips)")
     return ap.parse_args(argv)
 
@@ -640,7 +658,43 @@ WIRES = {"rccl": " (RCCL halos over xGMI)", "peer": " (device-initiated stores o
          "hosted": " (host-staged halos)"}
 
 
-def timed_solve_check(sh, m0):
+def finish_cg(sh):
+    """sm_cg_finish of the timed solve: the deferred x update, so the caller's x
+    holds the iterate of the last timed step; returns the CG's scalars."""
+    sm = sh.sm
+    res = sm.CGResult()
+    sm.check(sm.lib.sm_cg_finish(sh.L.ctx, ctypes.byref(res)))
+    return res
+
+
+DUMP_SEED, DUMP_MAX = 20240611, 1 << 21
+
+
+def dump_outputs(dirname, rt, res, fields):
+    """--dump-outputs: DIR/<name>.npy (float64) of what the timed path handed
+    back in its last step: `fields` (name -> device tensor; one above DUMP_MAX
+    values as the values at DUMP_MAX sorted indices drawn once from
+    numpy's default_rng(DUMP_SEED), the same for every field of one length
+    and from run to run) and the CG scalars (iterations, ||r||, ||phi||).
+    With N > 1 every rank writes its shard's files (<name>_shard<rank>.npy)."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    tag = f"_shard{rt['rank']}" if rt["world"] > 1 else ""
+    picks = {}
+    for name, t in fields.items():
+        n = t.numel()
+        if n > DUMP_MAX:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_MAX))
+                picks[n] = torch.from_numpy(idx).to(t.device)
+            t = t.index_select(0, picks[n])
+        np.save(os.path.join(dirname, f"{name}{tag}.npy"), t.cpu().numpy().astype(np.float64, copy=False))
+    np.save(os.path.join(dirname, f"cg_scalars{tag}.npy"),
+            np.array([res.iterations, res.residual, res.phi_norm], dtype=np.float64))
+
+
+def timed_solve_check(sh, m0, res=None):
     """N > 1: the timed solve checked against itself after the timing. The CG's
     recursive residual (sqrt <r,r> from the device scalars, the same on every
     shard) must agree with the true residual ||phi - D D^dag x|| / ||phi|| of
@@ -649,9 +703,7 @@ def timed_solve_check(sh, m0):
     iterations at tol 0 the two differ by rounding (~1e-13 of ||phi||) against
     a residual of ~1e-3, so the bar (1e-6 relative) is loose and still catches
     any wrong pass."""
-    sm = sh.sm
-    res = sm.CGResult()
-    sm.check(sm.lib.sm_cg_finish(sh.L.ctx, ctypes.byref(res)))
+    res = res or finish_cg(sh)
     rec = res.residual / res.phi_norm if res.phi_norm else float("nan")
     true = true_relres(sh, m0)
     ok = abs(true - rec) <= 1e-6 * rec
@@ -691,17 +743,22 @@ def run_config34(args, rt, cfg_id):
     apply_time = time_applies(rt, sh, m0, args.applies)
     t_cg, cg_bps = time_cg_steps(rt, sh, m0, args.cg_path, args.warmup, args.steps, args.no_link_angles, begun=True)
     apply_s = apply_time()
-    solve_check = timed_solve_check(sh, m0) if world > 1 else None
+    fin = finish_cg(sh) if world > 1 or args.dump_outputs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rt, fin, {"cg_x": sh.x, "dirac_out": sh.out})
+    solve_check = timed_solve_check(sh, m0, fin) if world > 1 else None
     t_cg, apply_s = max_over_ranks(rt, [t_cg, apply_s])
     if "probe_kept_us" in placement:
         # the probe times short bursts; the timed run sustains its own pass time
         # (both are reported)
         placement["sustained_us_per_pass"] = round(1e6 * t_cg / args.steps, 1)
     V = sh.V
-    evolved = time_evolved(args, rt, sh, cfg, m0) if world == 1 and args.evolved_trajectories > 0 else None
+    # everything below the headline's own timing is an extra of --full
+    evolved = (time_evolved(args, rt, sh, cfg, m0)
+               if args.full and world == 1 and args.evolved_trajectories > 0 else None)
     sh.close()
     weak = None
-    if not args.no_weak:
+    if args.full and not args.no_weak:
         # config 4's weak-scaling curve: 4096 x 512N sites, 4096 x 512 per GPU
         wNt = (Nt // 8) * world
         shw = Shard(rt, Nx, wNt, cfg["sigma"], sh.kind)
@@ -714,7 +771,7 @@ def run_config34(args, rt, cfg_id):
         shw.close()
     peer = None
     # (also beside the host-staged headline: the one-GPU rehearsal of this path)
-    if world > 1 and args.transport in ("rccl", "hosted") and not args.no_peer:
+    if args.full and world > 1 and args.transport in ("rccl", "hosted") and not args.no_peer:
         peer = time_peer(args, rt, Nx, Nt, cfg["sigma"], m0)
     if rank != 0:
         return
@@ -731,7 +788,7 @@ def run_config34(args, rt, cfg_id):
     # path timed on the same box's host cores"), on rank 0 after the GPU
     # timing: the same whole lattice, a bounded sample
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(dict(cfg, Nx=Nx, Nt=Nt), args.cpu_threads or cpu_share(), args.cpu_iters)
     bid = lib_build_id()
     tr = load_traffic(Nx, sh.Wt, bid)
@@ -793,6 +850,8 @@ def run_config5(args, rt):
     dt = time.perf_counter() - t
     (dt,) = max_over_ranks(rt, [dt])
     rel = true_relres(sh, m0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rt, res, {"cg_x": sh.x})
     cg_bps = cg_bytes_per_site(sh, args.cg_path)
     V = sh.V
     line = base_line(args, rt, cfg, Nx, Nt, sh)
