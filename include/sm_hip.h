@@ -222,6 +222,31 @@ int sm_cg_link_angles(sm_ctx *ctx, int on, int *in_use);
  * before the first pass. A later gauge upload or Metropolis reject does not
  * change it. The recompute-Ad pass streams 128 B/site besides. */
 int sm_cg_link_bytes(const sm_ctx *ctx, int *bytes_per_site);
+/* Precision of the solves that go through sm_cg_dev (sm_cg, sm_md_force(_dev),
+ * sm_leapfrog(_dev), sm_hamiltonian(_dev), sm_hmc_trajectory, sm_hmc_run):
+ * 0 = fp64 (default), 1 = mixed; < 0 keeps. SM_ERR_ARG on a sharded or loopback
+ * context (v1 is one shard) and for other values; *mode_out (nullable) = current.
+ * Mixed: the iterations run in fp32 (a recompute-Ad pass on float fields, 80
+ * instead of 145-160 B/site) on a correction y to x, and reliable updates hold
+ * the answer to the fp64 stop test: whenever the iterated residual has fallen
+ * by 10x, x += y and r = phi - D D^dag x is recomputed in fp64, and the search
+ * direction is kept across the replacement. The solve stops only on such a
+ * true residual (sm_cg_result.residual), so x passes the same stop test as the
+ * fp64 solve but is NOT the reference's iterate sequence: the two solutions
+ * differ by up to the stop test's slack (~tol relative), not by 1e-12.
+ * iterations counts the fp32 iterations plus any fp64 ones, and max_iter
+ * bounds that sum. If two consecutive updates fail to lower the true residual,
+ * or an fp32 scalar is not finite, the solve finishes in fp64 (D D^dag e = r,
+ * x += e). sm_cg_begin / iterate / finish and sm_eo_cg stay fp64. The fp32
+ * buffers are allocated at the first mixed solve. */
+int sm_cg_precision(sm_ctx *ctx, int mode, int *mode_out);
+typedef struct { int used; int inner_iterations; int reliable_updates;
+                 int fp64_iterations; int fell_back; double true_residual; } sm_cg_mixed_info;
+/* The last sm_cg_dev of the context: used = 1 if it ran mixed (else all zero),
+ * the fp32 iterations, the fp64 true residuals taken after the initial one,
+ * the iterations and the flag of the fp64 finish, and the last true residual
+ * ||phi - D D^dag x|| / ||phi||. */
+int sm_cg_mixed_last(const sm_ctx *ctx, sm_cg_mixed_info *out);  /* the last sm_cg_dev */
 /* Diagnostic (tests): encode every link of the context's current U and decode
  * it again ON THE DEVICE with the CG pass's own functions. Writes the rebuilt
  * links to U_out_dev (device, the layout of sm_upload_gauge_dev; may be NULL),

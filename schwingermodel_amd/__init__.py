@@ -25,7 +25,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import CGResult, HamiltonianTerms, HMCParams, HMCResult, HMCSummary, SMError, check, lib
+from ._lib import CGMixedInfo, CGResult, HamiltonianTerms, HMCParams, HMCResult, HMCSummary, SMError, check, lib
 
 __all__ = ["spinor", "re_field", "c_double", "I_number", "CG", "init", "lattice", "Lattice",
            "D_phi", "D_dagger_phi", "D_D_dagger_phi", "phi_dag_partialD_phi",
@@ -39,6 +39,7 @@ class CG:
     """Mirror of namespace CG (src/variables.cpp:35-38; set in src/main.cpp:26-27)."""
     max_iter = 10000
     tol = 1e-10
+    precision = "double"  # or "mixed" (Lattice.cg_precision; not in the reference)
 
 
 def _vp(a):
@@ -115,6 +116,28 @@ class Lattice:
         t, n, r = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(lib.sm_comm_info(self.ctx, ctypes.byref(t), ctypes.byref(n), ctypes.byref(r)))
         return self.TRANSPORTS[t.value], n.value, r.value
+
+    PRECISIONS = {"double": 0, "mixed": 1}
+
+    def cg_precision(self, mode=None):
+        """Set ("double" / "mixed", or 0 / 1) and return the precision of the
+        solves that go through sm_cg_dev (sm_cg_precision; None only reads).
+        Mixed runs on one-shard contexts: fp32 iterations held to the fp64
+        stop test by reliable updates, so x passes the same test but is not
+        the reference's iterate sequence."""
+        m = -1 if mode is None else self.PRECISIONS.get(mode, mode)
+        if not isinstance(m, int):
+            raise ValueError(f"CG precision {mode!r}: 'double' or 'mixed'")
+        cur = ctypes.c_int()
+        check(lib.sm_cg_precision(self.ctx, m, ctypes.byref(cur)))
+        return "mixed" if cur.value == 1 else "double"
+
+    @property
+    def last_cg_mixed(self):
+        """sm_cg_mixed_info of the context's last sm_cg_dev (used = 0: it ran fp64)."""
+        info = CGMixedInfo()
+        check(lib.sm_cg_mixed_last(self.ctx, ctypes.byref(info)))
+        return info
 
     def close(self):
         if self.ctx:
@@ -219,6 +242,8 @@ def conjugate_gradient(U, phi, x, m0):
         x.mu1 = np.zeros_like(phi.mu1)
         x.size = phi.size
     L.upload_gauge(U)
+    if L.cg_precision() != CG.precision:
+        L.cg_precision(CG.precision)
     res = CGResult()
     check(lib.sm_cg(L.ctx, _vp(phi.mu0), _vp(phi.mu1), _vp(x.mu0), _vp(x.mu1), float(m0),
                     float(CG.tol), int(CG.max_iter), ctypes.byref(res)))

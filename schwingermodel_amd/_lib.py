@@ -46,6 +46,11 @@ class HMCResult(ctypes.Structure):
                 ("cg_failures", ctypes.c_int)]
 
 
+class CGMixedInfo(ctypes.Structure):
+    _fields_ = [("used", ctypes.c_int), ("inner_iterations", ctypes.c_int), ("reliable_updates", ctypes.c_int),
+                ("fp64_iterations", ctypes.c_int), ("fell_back", ctypes.c_int), ("true_residual", ctypes.c_double)]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(f"{LIB_PATH} not built: run `python -c 'import __graft_entry__ as g; g.build()'`"
@@ -110,6 +115,8 @@ def _load():
         "sm_cg_link_angles": ([vp, ci, ctypes.POINTER(ci)], ci),
         "sm_link_code_check": ([vp, vp, ctypes.POINTER(cd), ctypes.POINTER(ctypes.c_long)], ci),
         "sm_cg_link_bytes": ([vp, ctypes.POINTER(ci)], ci),
+        "sm_cg_precision": ([vp, ci, ctypes.POINTER(ci)], ci),
+        "sm_cg_mixed_last": ([vp, ctypes.POINTER(CGMixedInfo)], ci),
         "sm_tune_cg_geometry": ([vp, ci, ci], ci),
         "sm_tune_cg_strip": ([vp, ci, ci], ci),
         # gauge field / molecular dynamics / HMC

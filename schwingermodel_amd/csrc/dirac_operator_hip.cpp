@@ -105,6 +105,19 @@ std::string transport_choice(int local_leaders, int ndev) {
     return t;
 }
 
+// SM_DROPIN_CG_PRECISION=mixed: conjugate_gradient runs the mixed-precision
+// solve (sm_cg_precision): x passes the same stop test, but is not the
+// reference's iterate sequence. One t-shard only.
+bool cg_precision_mixed() {
+    const char *e = std::getenv("SM_DROPIN_CG_PRECISION");
+    const std::string p = e ? e : "double";
+    if (p != "double" && p != "mixed") {
+        std::cerr << "[sm_hip] SM_DROPIN_CG_PRECISION must be double or mixed" << std::endl;
+        MPI_Abort(MPI_COMM_WORLD, 1);
+    }
+    return p == "mixed";
+}
+
 Shim &shim() {
     if (g.col != MPI_COMM_NULL) return g;
     g.ncol = mpi::ranks_x;
@@ -116,6 +129,12 @@ Shim &shim() {
     MPI_Comm_split(mpi::cart_comm, mpi::coords[1], mpi::coords[0], &g.col);
     MPI_Comm_split(mpi::cart_comm, g.leader ? 0 : MPI_UNDEFINED, mpi::coords[1], &g.lead);
     g.lastU.assign((size_t)4 * g.Vloc, 0.0);
+    const bool mixed = cg_precision_mixed();
+    if (mixed && g.nshard > 1) {
+        std::cerr << "[sm_hip] SM_DROPIN_CG_PRECISION=mixed needs ranks_t = 1 (the mixed-precision CG is one shard)"
+                  << std::endl;
+        MPI_Abort(MPI_COMM_WORLD, 1);
+    }
     if (!g.leader) return g;
     if (g.ncol > 1) {
         for (auto *v : {&g.U, &g.a, &g.b, &g.c}) v->assign((size_t)4 * g.Vcol, 0.0);
@@ -132,6 +151,7 @@ Shim &shim() {
     const int device = local % ndev;
     if (g.nshard == 1) {
         call(sm_create(&g.ctx, LV::Nx, LV::Nt, 1, 0, device, nullptr), "sm_create");
+        if (mixed) call(sm_cg_precision(g.ctx, 1, nullptr), "sm_cg_precision");
     } else if (const std::string t = transport_choice(nlocal, ndev); t == "mpi") {
         g.tr.user = nullptr;
         g.tr.exchange = mpi_exchange;

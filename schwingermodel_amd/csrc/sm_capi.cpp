@@ -265,6 +265,10 @@ int sm_comm_unique_id(void *id_out, int id_bytes) {
 //   bt=64|128|256       Dirac apply t-columns per block
 //   eo_fused=0, eo_cg_td=0, eo_cg_folded=1   even-odd operator / CG forms
 //   debug_cg=1          CG host loops print their status (stderr)
+//   mp_force_fallback=1 mixed-precision CG: take the fp64 finish after the first
+//                       reliable update
+//   mp_delta_pct=N      mixed-precision CG: reliable update when the iterated
+//                       residual is below N % of its maximum (default 10)
 // An unknown key or a malformed value fails the creation.
 static int apply_test_opts(sm_ctx *c) {
     const char *env = getenv("SM_TEST_OPTS");
@@ -352,6 +356,11 @@ static int apply_test_opts(sm_ctx *c) {
             c->eo_cg_folded = iv;
         } else if (k == "debug_cg") {
             c->debug_cg = iv;
+        } else if (k == "mp_force_fallback") {
+            c->mp_force_fallback = iv ? 1 : 0;
+        } else if (k == "mp_delta_pct") {
+            if (iv < 1 || iv > 99) return fail(SM_ERR_ARG, "SM_TEST_OPTS: mp_delta_pct must be 1..99");
+            c->mp_delta = 0.01 * iv;
         } else {
             return fail(SM_ERR_ARG, "SM_TEST_OPTS: unknown key '%s'", k.c_str());
         }
@@ -604,6 +613,7 @@ int sm_destroy(sm_ctx *c) {
         }
     stream_free(c, c->Uang);
     c->Uang = nullptr;
+    cg_mixed_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};
@@ -1267,6 +1277,31 @@ int sm_cg_status(sm_ctx *c, sm_cg_result *res) {
 int sm_cg_dev(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter,
               sm_cg_result *res) {
     if (!res) return fail(SM_ERR_ARG, "null result");
+    if (c) c->mp_info = sm_cg_mixed_info{};
+    if (c && c->cg_precision == 1) return cg_dev_mixed(c, phi, x, m0, tol, max_iter, res);
+    return cg_dev_fp64(c, phi, x, m0, tol, max_iter, res);
+}
+
+int sm_cg_precision(sm_ctx *c, int mode, int *mode_out) {
+    if (!c) return fail(SM_ERR_ARG, "null context");
+    int rc = SM_OK;
+    if (mode > 1) rc = fail(SM_ERR_ARG, "CG precision must be 0 (fp64) or 1 (mixed)");
+    else if (mode == 1 && c->sharded()) rc = fail(SM_ERR_ARG, "the mixed-precision CG runs on one-shard contexts");
+    else if (mode >= 0) c->cg_precision = mode;
+    if (mode_out) *mode_out = c->cg_precision;
+    return rc;
+}
+
+int sm_cg_mixed_last(const sm_ctx *c, sm_cg_mixed_info *out) {
+    if (!c || !out) return fail(SM_ERR_ARG, "null argument");
+    *out = c->mp_info;
+    return SM_OK;
+}
+
+}  // extern "C"
+
+int sm_host::cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter,
+                         sm_cg_result *res) {
     TRY(sm_cg_begin(c, phi, x, m0, tol));
     // Enqueue iterations in chunks; each CG kernel is a no-op once the device
     // flag `done` is set, so overshooting a chunk costs only empty launches.
@@ -1292,6 +1327,8 @@ int sm_cg_dev(sm_ctx *c, const double *phi, double *x, double m0, double tol, in
     }
     return sm_cg_finish(c, res);
 }
+
+extern "C" {
 
 // ---- host-pointer (drop-in) operators ---------------------------------------
 int sm_dirac(sm_ctx *c, const double *in0, const double *in1, double *out0, double *out1, double m0,

@@ -195,6 +195,21 @@ struct sm_ctx {
     int cg_active = 0;
     long cg_issued = 0;             // iterations enqueued since sm_cg_begin
     int cg_pending_x = 0;           // fused path: last x update deferred to sm_cg_finish
+    // mixed-precision CG (sm_cgmp.cpp; one shard): sm_cg_dev runs fp32 inner
+    // iterations with fp64 reliable updates when cg_precision == 1. Buffers
+    // from the first mixed solve on; its own scalars, partials and directions
+    // (nothing shared with the fp64 paths).
+    int cg_precision = 0;
+    double mp_delta = 0.1;          // update when the iterated |r| < mp_delta * its maximum (test option mp_delta_pct)
+    int mp_force_fallback = 0;      // test option: take the fp64 finish after the first update
+    float2 *mp_d[3] = {};           // the three direction buffers, 2V float2 each
+    float2 *mp_y = nullptr;         // the fp32 correction to x
+    float2 *mp_U = nullptr;         // the links as the fp32 pass reads them
+    bool mp_U_valid = false;        // false after every change of U (exchange_ghost_U)
+    double2 *mp_partials = nullptr; // 2 per tile
+    double2 *mp_fb = nullptr;       // fp64 finish: rhs and correction (4V complex; allocated on a fallback)
+    sm::MPScalars *mp_sc = nullptr, *mp_h_sc = nullptr;  // device, pinned host mirror
+    sm_cg_mixed_info mp_info{};     // the last sm_cg_dev
 
     double2 *field(int i) { return fields[i]; }
 };
@@ -293,6 +308,12 @@ void stream_free(sm_ctx *c, void *p);
 size_t link_code_bytes(long n);           // codes of n links (sm_linkcode.h), flag words and flag bytes
 int placement_probe(sm_ctx *c, size_t fb);
 int placement_probe_default();            // candidates per buffer for new contexts
+
+// sm_cg_dev's fp64 solve (sm_capi.cpp), and the mixed-precision one it hands
+// to when the context's cg_precision is 1 (sm_cgmp.cpp)
+int cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
+int cg_dev_mixed(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
+void cg_mixed_free(sm_ctx *c);
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

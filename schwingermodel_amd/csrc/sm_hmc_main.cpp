@@ -129,6 +129,13 @@ int main(int argc, char **argv) {
     const char *te = std::getenv("SM_HMC_TRANSPORT");
     const std::string transport = te ? te : "rccl";
     if (transport != "peer" && transport != "rccl") die("SM_HMC_TRANSPORT must be peer or rccl");
+    // SM_HMC_CG_PRECISION=mixed: fp32 CG iterations with fp64 reliable updates
+    // (sm_cg_precision; one rank only, and not the even-odd action's solver)
+    const char *pe = std::getenv("SM_HMC_CG_PRECISION");
+    const std::string precision = pe ? pe : "double";
+    if (precision != "double" && precision != "mixed") die("SM_HMC_CG_PRECISION must be double or mixed");
+    if (precision == "mixed" && size > 1)
+        die("SM_HMC_CG_PRECISION=mixed runs on one rank (the mixed-precision CG is one shard)");
     sm_ctx *ctx = nullptr;
     if (size > 1 && transport == "peer") {
         const int nb = sm_peer_handle_bytes();
@@ -144,6 +151,7 @@ int main(int argc, char **argv) {
         }
         if (sm_create(&ctx, Nx, Nt, size, rank, local % ndev, size > 1 ? uid : nullptr) != SM_OK) die("sm_create");
     }
+    if (precision == "mixed" && sm_cg_precision(ctx, 1, nullptr) != SM_OK) die("sm_cg_precision");
 
     std::string start_time_str;
     if (rank == 0) {

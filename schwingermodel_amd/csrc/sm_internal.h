@@ -215,6 +215,46 @@ void launch_pack_faces2(hipStream_t s, const Geometry &g, const double2 *field, 
 void launch_stream(hipStream_t s, int two, long n, const double2 *a, const double2 *b, double2 *out,
                    int blocks);
 
+// ---- mixed-precision CG (sm_cgsp.hip; driver sm_cgmp.cpp) ----
+// Device-resident scalars of a mixed solve: a segment of fp32 inner iterations
+// between two fp64 true residuals (reliable updates). alpha and beta are real.
+struct MPScalars {
+    double alpha, beta;      // alpha_j, beta_j after pass j's scalar step (beta: the injection's before pass 0)
+    double alpha2, beta2;    // those of the pass before
+    double rn;               // iterated |r|^2 of the previous iteration
+    double err;              // iterated |r| of the last iteration
+    double M;                // largest iterated |r| since the segment began (starts at the true |r|)
+    double phi_norm, tol, delta;
+    double true_rr, phi_rr;  // |phi - D D^dag x|^2 (fp64) of the last update, |phi|^2
+    int k;                   // inner iterations of this segment
+    int k_total;             // inner iterations of the solve
+    int max_iter;            // bound on k_total
+    int done;                // the segment is over: every later pass and scalar step is a no-op
+    int bad;                 // it ended on a non-finite scalar (or <d,Ad> <= 0)
+    int pad;
+};
+// The fp32 pass's tiles: the recompute-Ad pass's shape (ra) without its t-strips.
+CGFusedCfg cg_sp_config(const Geometry &g, const CGFusedCfg &ra);
+// Pass `pass` of a segment (0: the injected direction, no store): d_{j-1} in
+// d1, d_{j-2} in d2, d_j to dn; 2 partials per tile for launch_cg_sp_scalars.
+void launch_cg_sp(hipStream_t s, const Geometry &g, const CGFusedCfg &c, const float2 *d1, const float2 *d2, float2 *dn,
+                  float2 *y, const float2 *U32, double mass, long pass, MPScalars *sc, double2 *partials);
+void launch_cg_sp_scalars(hipStream_t s, int ntiles, const double2 *partials, MPScalars *sc, int first);
+// U32 = the links as the fp32 pass reads them (pre-scaled, sm_cgsp.hip)
+void launch_sp_convert_links(hipStream_t s, const Geometry &g, const double2 *U, float2 *U32);
+// r = phi - Ax with per-block (|r|^2, |phi|^2); returns the block count
+int launch_mp_residual(hipStream_t s, long n, const double2 *phi, const double2 *Ax, double2 *r, double2 *partials);
+// those partials into sc: the true residual, the stop test, the next segment's M and injection beta
+void launch_mp_update(hipStream_t s, int nparts, const double2 *partials, MPScalars *sc, int init, int restart,
+                      double tol, double delta, int max_iter);
+// d0 = r + sc->beta dprev in fp32 (sc->beta == 0: dprev = d0 = r)
+void launch_mp_inject(hipStream_t s, long n, const double2 *r, float2 *dprev, float2 *d0, const MPScalars *sc);
+// x += y plus the pending alpha_{J-1} d_{J-1} rows (dlast = d_{J-1}), y = 0; discard: y = 0 only
+void launch_mp_fold(hipStream_t s, const Geometry &g, double2 *x, float2 *y, const float2 *dlast, const MPScalars *sc,
+                    int discard);
+void launch_mp_add(hipStream_t s, long n, double2 *x, const double2 *e);
+void launch_mp_zero(hipStream_t s, long n, float2 *y);
+
 // ---- gauge field / molecular dynamics (sm_gauge.hip) ----
 // fU: the 2-deep U faces (nshard > 1; ignored for one shard, which wraps).
 int gauge_reduce_blocks(const Geometry &g);
