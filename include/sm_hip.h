@@ -237,7 +237,8 @@ int sm_cg_link_bytes(const sm_ctx *ctx, int *bytes_per_site);
  * iterations counts the fp32 iterations plus any fp64 ones, and max_iter
  * bounds that sum. If two consecutive updates fail to lower the true residual,
  * or an fp32 scalar is not finite, the solve finishes in fp64 (D D^dag e = r,
- * x += e). sm_cg_begin / iterate / finish and sm_eo_cg stay fp64. The fp32
+ * x += e). sm_cg_begin / iterate / finish stay fp64; the even-odd solver has
+ * its own switch (sm_eo_cg_precision below), independent of this one. The fp32
  * buffers are allocated at the first mixed solve. */
 int sm_cg_precision(sm_ctx *ctx, int mode, int *mode_out);
 typedef struct { int used; int inner_iterations; int reliable_updates;
@@ -470,6 +471,30 @@ int sm_eo_dhat(sm_ctx *ctx, int dagger, const double *in0, const double *in1, do
                double m0);
 int sm_eo_cg(sm_ctx *ctx, const double *phi0, const double *phi1, double *x0, double *x1, double m0, double tol,
              int max_iter, sm_cg_result *res);
+/* sm_eo_cg on device-resident full-layout fields (the layout of sm_cg_dev): no
+ * host transfers; x's odd sites are set to 0. Synchronous. */
+int sm_eo_cg_dev(sm_ctx *ctx, const double *phi, double *x, double m0, double tol, int max_iter,
+                 sm_cg_result *res);
+/* Precision of the even-odd solver: sm_eo_cg(_dev) and every even-odd solve inside
+ * sm_md_force(_dev), sm_leapfrog(_dev), sm_hamiltonian(_dev), sm_hmc_trajectory
+ * and sm_hmc_run when p->even_odd = 1. 0 = fp64 (default), 1 = mixed; < 0
+ * keeps. SM_ERR_ARG (mode stays 0) on sharded, loopback and peer contexts and
+ * for other values; *mode_out (nullable) = current. Independent of
+ * sm_cg_precision: either switch changes only its own solver.
+ * Mixed: the scheme of sm_cg_precision on Dhat Dhat^dag. The iterations run
+ * the one-pass even-odd kernel on float2 checkerboard fields (128 instead of
+ * 256 B per even site) on a correction y to x; whenever the iterated residual
+ * has fallen by 10x, x += y and r = phi_e - Dhat Dhat^dag x is recomputed in
+ * fp64, and the search direction is kept. The solve stops only on such a true
+ * residual, so x passes the fp64 stop test but is not the fp64 iterate
+ * sequence. iterations = fp32 + fp64 iterations, bounded by max_iter. Two
+ * consecutive updates that fail to lower the true residual, or a bad fp32
+ * scalar, finish in fp64 (Dhat Dhat^dag e = r through the fp64 even-odd CG,
+ * x += e). The fp32 buffers are allocated at the first mixed even-odd solve. */
+int sm_eo_cg_precision(sm_ctx *ctx, int mode, int *mode_out);
+/* The context's last even-odd solve, as sm_cg_mixed_last: all zero if it ran
+ * fp64; true_residual = ||phi_e - Dhat Dhat^dag x|| / ||phi_e||. */
+int sm_eo_cg_mixed_last(const sm_ctx *ctx, sm_cg_mixed_info *out);
 
 /* Gather the sharded gauge field to shard 0 (SaveConf's MPI_Gatherv,
  * src/gauge_conf.cpp:378-396): U0/U1 on shard 0 receive the global

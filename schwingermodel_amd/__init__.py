@@ -139,6 +139,25 @@ class Lattice:
         check(lib.sm_cg_mixed_last(self.ctx, ctypes.byref(info)))
         return info
 
+    def eo_cg_precision(self, mode=None):
+        """Set ("double" / "mixed", or 0 / 1) and return the precision of the
+        even-odd solver: sm_eo_cg and the even-odd action's solves
+        (sm_eo_cg_precision; None only reads). Independent of cg_precision;
+        one-shard contexts only."""
+        m = -1 if mode is None else self.PRECISIONS.get(mode, mode)
+        if not isinstance(m, int):
+            raise ValueError(f"even-odd CG precision {mode!r}: 'double' or 'mixed'")
+        cur = ctypes.c_int()
+        check(lib.sm_eo_cg_precision(self.ctx, m, ctypes.byref(cur)))
+        return "mixed" if cur.value == 1 else "double"
+
+    @property
+    def last_eo_cg_mixed(self):
+        """sm_cg_mixed_info of the context's last even-odd solve (used = 0: it ran fp64)."""
+        info = CGMixedInfo()
+        check(lib.sm_eo_cg_mixed_last(self.ctx, ctypes.byref(info)))
+        return info
+
     def close(self):
         if self.ctx:
             lib.sm_destroy(self.ctx)

@@ -117,6 +117,9 @@ def _load():
         "sm_cg_link_bytes": ([vp, ctypes.POINTER(ci)], ci),
         "sm_cg_precision": ([vp, ci, ctypes.POINTER(ci)], ci),
         "sm_cg_mixed_last": ([vp, ctypes.POINTER(CGMixedInfo)], ci),
+        "sm_eo_cg_dev": ([vp, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
+        "sm_eo_cg_precision": ([vp, ci, ctypes.POINTER(ci)], ci),
+        "sm_eo_cg_mixed_last": ([vp, ctypes.POINTER(CGMixedInfo)], ci),
         "sm_tune_cg_geometry": ([vp, ci, ci], ci),
         "sm_tune_cg_strip": ([vp, ci, ci], ci),
         # gauge field / molecular dynamics / HMC

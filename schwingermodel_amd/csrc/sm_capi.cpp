@@ -614,6 +614,7 @@ int sm_destroy(sm_ctx *c) {
     stream_free(c, c->Uang);
     c->Uang = nullptr;
     cg_mixed_free(c);
+    eo_cg_mixed_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};

@@ -210,6 +210,23 @@ struct sm_ctx {
     double2 *mp_fb = nullptr;       // fp64 finish: rhs and correction (4V complex; allocated on a fallback)
     sm::MPScalars *mp_sc = nullptr, *mp_h_sc = nullptr;  // device, pinned host mirror
     sm_cg_mixed_info mp_info{};     // the last sm_cg_dev
+    // mixed-precision even-odd CG (sm_eomp.cpp; one shard): every even-odd
+    // solve runs fp32 inner iterations (sm_eosp.hip) with fp64 reliable updates
+    // when eo_cg_precision == 1. Independent of cg_precision; shares only the
+    // test options mp_delta / mp_force_fallback. Its buffers (from the first
+    // mixed even-odd solve on) are its own: neither eo / sc / partials / tick
+    // nor the mp_* state above is touched by the fp32 side.
+    int eo_cg_precision = 0;
+    float2 *eomp_d[3] = {};         // the three direction buffers, V float2 each (one parity)
+    float2 *eomp_a[2] = {};         // Ad_j by pass parity
+    float2 *eomp_y = nullptr;       // the fp32 correction to x
+    float2 *eomp_U[2] = {};         // even / odd links as the fp32 pass reads them
+    bool eomp_U_valid = false;      // false after every change of U (exchange_ghost_U)
+    double2 *eomp_w = nullptr;      // fp64 work: r, Dhat^dag x, Dhat Dhat^dag x (3V complex)
+    double2 *eomp_fb = nullptr;     // fp64 finish: rhs and correction (2V complex; allocated on a fallback)
+    double2 *eomp_partials = nullptr;
+    sm::MPScalars *eomp_sc = nullptr, *eomp_h_sc = nullptr;  // device, pinned host mirror
+    sm_cg_mixed_info eomp_info{};   // the last even-odd solve
 
     double2 *field(int i) { return fields[i]; }
 };
@@ -318,6 +335,16 @@ void cg_mixed_free(sm_ctx *c);
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used
 int eo_ready(sm_ctx *c);
+// the fp64 building blocks the mixed even-odd solve (sm_eomp.cpp) stands on:
+// out_e = Dhat v_e / Dhat^dag v_e, and the fp64 CG on Dhat Dhat^dag (x0 = b)
+int eo_dhat(sm_ctx *c, int dagger, const double2 *v, double2 *out, double mass, const double2 *aux = nullptr,
+            double2 *partials = nullptr, int *nparts = nullptr);
+int eo_cg(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res);
+const double2 *eo_links(sm_ctx *c, int parity);  // the checkerboard links eo_ready made of the current U
+// every even-odd solve of the library: eo_cg, or eo_cg_mixed when eo_cg_precision == 1
+int eo_solve(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res);
+int eo_cg_mixed(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res);
+void eo_cg_mixed_free(sm_ctx *c);
 int eo_md_force(sm_ctx *c, const sm_hmc_params *p, const double2 *phi_full, double *F, sm_cg_result *res);
 int eo_fermion_action(sm_ctx *c, const sm_hmc_params *p, const double2 *phi_full, double *S, sm_cg_result *res);
 int eo_pseudofermion(sm_ctx *c, const sm_hmc_params *p, const double2 *chi_full, double2 *phi_full);

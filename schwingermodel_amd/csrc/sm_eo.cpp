@@ -126,8 +126,8 @@ int eo_ready(sm_ctx *c) {
 // of sum aux * conj(out); unfused (c->eo_fused == 0): two eo_hop launches
 // through EO_T, bitwise the same result. t-sharded: v's faces go to slot
 // EOF_V first (and T's to EOF_W unfused). *nparts: the partial count.
-int eo_dhat(sm_ctx *c, int dagger, const double2 *v, double2 *out, double mass, const double2 *aux = nullptr,
-            double2 *partials = nullptr, int *nparts = nullptr) {
+int eo_dhat(sm_ctx *c, int dagger, const double2 *v, double2 *out, double mass, const double2 *aux, double2 *partials,
+            int *nparts) {
     EoFaces f = u_faces(c);
     TRY(eo_halo(c, v, EOF_V, &f.v));
     if (c->eo_fused) {
@@ -376,6 +376,17 @@ int eo_cg(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int 
     return SM_OK;
 }
 
+const double2 *eo_links(sm_ctx *c, int parity) { return ucb(c, parity); }
+
+// Every even-odd solve of the library comes through here: the fp64 CG above,
+// or fp32 inner iterations with fp64 reliable updates (sm_eomp.cpp) when the
+// context's eo_cg_precision is 1 (sm_eo_cg_precision).
+int eo_solve(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res) {
+    c->eomp_info = sm_cg_mixed_info{};
+    if (c->eo_cg_precision == 1) return eo_cg_mixed(c, b, x, mass, tol, max_iter, res);
+    return eo_cg(c, b, x, mass, tol, max_iter, res);
+}
+
 // phi (full layout) -> its even part in EO_PHI
 static void eo_take_even(sm_ctx *c, const double2 *full, double2 *e) {
     launch_to_cb(c->stream, c->g, full, e, nullptr);
@@ -388,7 +399,7 @@ int eo_md_force(sm_ctx *c, const sm_hmc_params *p, const double2 *phi_full, doub
     double2 *phie = eo_vec(c, EO_PHI), *X = eo_vec(c, EO_X), *Y = eo_vec(c, EO_Y);
     double2 *lo = eo_vec(c, EO_LO), *ro = eo_vec(c, EO_RO);
     eo_take_even(c, phi_full, phie);
-    TRY(eo_cg(c, phie, X, m, p->cg_tol, p->cg_max_iter, res));
+    TRY(eo_solve(c, phie, X, m, p->cg_tol, p->cg_max_iter, res));
     TRY(eo_dhat(c, 1, X, Y, m));                                                        // Y = Dhat^dag X
     const EoFaces f = u_faces(c);
     const double2 *xf, *yf;
@@ -410,7 +421,7 @@ int eo_fermion_action(sm_ctx *c, const sm_hmc_params *p, const double2 *phi_full
     const double m = p->m0 + 2;
     double2 *phie = eo_vec(c, EO_PHI), *X = eo_vec(c, EO_X);
     eo_take_even(c, phi_full, phie);
-    TRY(eo_cg(c, phie, X, m, p->cg_tol, p->cg_max_iter, res));
+    TRY(eo_solve(c, phie, X, m, p->cg_tol, p->cg_max_iter, res));
     // dot over the V complex entries of an even vector (sm_dot_dev spans 2V)
     launch_dot_partial(c->stream, c->g.V, X, phie, c->partials);
     TRY(global_sum(c, reduce_blocks(c->g.V), c->partials, 0));
@@ -461,10 +472,41 @@ int sm_eo_cg(sm_ctx *c, const double *phi0, const double *phi1, double *x0, doub
     TRY(upload_plane_pair(c, in, phi0, phi1));
     double2 *phie = eo_vec(c, EO_PHI), *X = eo_vec(c, EO_X);
     eo_take_even(c, in, phie);
-    TRY(eo_cg(c, phie, X, m0 + 2, tol, max_iter, res));
+    TRY(eo_solve(c, phie, X, m0 + 2, tol, max_iter, res));
     launch_from_cb(c->stream, c->g, X, nullptr, out);
     HIP_TRY(hipGetLastError());
     return download_plane_pair(c, out, x0, x1);
+}
+
+int sm_eo_cg_dev(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res) {
+    TRY(check_ready(c));
+    if (!phi || !x || !res) return fail(SM_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
+    TRY(eo_ready(c));
+    double2 *phie = eo_vec(c, EO_PHI), *X = eo_vec(c, EO_X);
+    eo_take_even(c, (const double2 *)phi, phie);
+    TRY(eo_solve(c, phie, X, m0 + 2, tol, max_iter, res));
+    launch_from_cb(c->stream, c->g, X, nullptr, (double2 *)x);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return SM_OK;
+}
+
+int sm_eo_cg_precision(sm_ctx *c, int mode, int *mode_out) {
+    if (!c) return fail(SM_ERR_ARG, "null context");
+    int rc = SM_OK;
+    if (mode > 1) rc = fail(SM_ERR_ARG, "even-odd CG precision must be 0 (fp64) or 1 (mixed)");
+    else if (mode == 1 && (c->sharded() || c->peer))
+        rc = fail(SM_ERR_ARG, "the mixed-precision even-odd CG runs on one-shard contexts");
+    else if (mode >= 0) c->eo_cg_precision = mode;
+    if (mode_out) *mode_out = c->eo_cg_precision;
+    return rc;
+}
+
+int sm_eo_cg_mixed_last(const sm_ctx *c, sm_cg_mixed_info *out) {
+    if (!c || !out) return fail(SM_ERR_ARG, "null argument");
+    *out = c->eomp_info;
+    return SM_OK;
 }
 
 }  // extern "C"

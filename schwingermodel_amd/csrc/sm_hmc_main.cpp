@@ -130,12 +130,21 @@ int main(int argc, char **argv) {
     const std::string transport = te ? te : "rccl";
     if (transport != "peer" && transport != "rccl") die("SM_HMC_TRANSPORT must be peer or rccl");
     // SM_HMC_CG_PRECISION=mixed: fp32 CG iterations with fp64 reliable updates
-    // (sm_cg_precision; one rank only, and not the even-odd action's solver)
+    // (sm_cg_precision; one rank only; the full action's solver).
+    // SM_HMC_EO_CG_PRECISION=mixed: the same for the even-odd action's solver
+    // (sm_eo_cg_precision; needs --even-odd and one rank)
     const char *pe = std::getenv("SM_HMC_CG_PRECISION");
     const std::string precision = pe ? pe : "double";
     if (precision != "double" && precision != "mixed") die("SM_HMC_CG_PRECISION must be double or mixed");
     if (precision == "mixed" && size > 1)
         die("SM_HMC_CG_PRECISION=mixed runs on one rank (the mixed-precision CG is one shard)");
+    const char *pee = std::getenv("SM_HMC_EO_CG_PRECISION");
+    const std::string eo_precision = pee ? pee : "double";
+    if (eo_precision != "double" && eo_precision != "mixed") die("SM_HMC_EO_CG_PRECISION must be double or mixed");
+    if (eo_precision == "mixed" && !even_odd)
+        die("SM_HMC_EO_CG_PRECISION=mixed needs --even-odd (it sets the even-odd action's solver)");
+    if (eo_precision == "mixed" && size > 1)
+        die("SM_HMC_EO_CG_PRECISION=mixed runs on one rank (the mixed-precision even-odd CG is one shard)");
     sm_ctx *ctx = nullptr;
     if (size > 1 && transport == "peer") {
         const int nb = sm_peer_handle_bytes();
@@ -152,6 +161,7 @@ int main(int argc, char **argv) {
         if (sm_create(&ctx, Nx, Nt, size, rank, local % ndev, size > 1 ? uid : nullptr) != SM_OK) die("sm_create");
     }
     if (precision == "mixed" && sm_cg_precision(ctx, 1, nullptr) != SM_OK) die("sm_cg_precision");
+    if (eo_precision == "mixed" && sm_eo_cg_precision(ctx, 1, nullptr) != SM_OK) die("sm_eo_cg_precision");
 
     std::string start_time_str;
     if (rank == 0) {

@@ -329,6 +329,21 @@ void launch_eo_td(hipStream_t s, const Geometry &g, const EoTdCfg &c, const doub
                   int red = 0);  // red: t-shard scalars from sc->sumr (out3 = this pass's sumr slot)
 void launch_pack_cb_faces4(hipStream_t s, const Geometry &g, const double2 *f, double2 *out);
 
+// ---- mixed-precision even-odd CG (sm_eosp.hip; driver sm_eomp.cpp) ----
+// Pass `pass` of a segment on float2 checkerboard fields (0: the injected
+// direction, no d store; even passes >= 2 update y): d_{j-1} in d1, d_{j-2} in
+// d2, Ad_{j-1} in aold (not read by pass 0), d_j to dn, Ad_j to anew; the
+// eo_td_config tiles, 2 partials per block for launch_cg_sp_scalars.
+void launch_eo_sp(hipStream_t s, const Geometry &g, const EoTdCfg &c, const float2 *d1, const float2 *d2,
+                  const float2 *aold, float2 *dn, float2 *anew, float2 *y, const float2 *Ue32, const float2 *Uo32,
+                  double mass, long pass, const MPScalars *sc, double2 *partials);
+// the checkerboard links as the fp32 pass reads them (pre-scaled, signed; sm_eosp.hip)
+void launch_eo_sp_convert_links(hipStream_t s, const Geometry &g, const double2 *Ue, const double2 *Uo, float2 *Ue32,
+                                float2 *Uo32);
+// x += y plus the pending alpha_{J-1} d_{J-1} after an odd last pass (dlast = d_{J-1}), y = 0; discard: y = 0 only
+void launch_eo_mp_fold(hipStream_t s, long n, double2 *x, float2 *y, const float2 *dlast, const MPScalars *sc,
+                       int discard);
+
 // Pack the t = 0 and t = Wt-1 columns (both planes) into contiguous faces.
 void launch_pack_faces(hipStream_t s, const Geometry &g, const double2 *field, double2 *lo_face,
                        double2 *hi_face);
