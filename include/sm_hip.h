@@ -496,6 +496,62 @@ int sm_eo_cg_precision(sm_ctx *ctx, int mode, int *mode_out);
  * fp64; true_residual = ||phi_e - Dhat Dhat^dag x|| / ||phi_e||. */
 int sm_eo_cg_mixed_last(const sm_ctx *ctx, sm_cg_mixed_info *out);
 
+/* ==== batched multi-source CG and the pion correlator =======================
+ * D D^dag x_b = phi_b for K right-hand sides on the context's current gauge
+ * field, ONE launch per iteration for the whole batch (schwingermodel_amd/
+ * csrc/sm_cgbatch.hip). Below 256^2 a lone solve's iteration costs the same
+ * 11-12 us whatever the lattice (launch + each block's dependent loads); K
+ * columns share that cost. Each column runs the stored-Ad two-direction
+ * iteration of sm_tune_cg's fused = 4 -- the reference's iterate sequence
+ * (src/conjugate_gradient.cpp:31-63, x0 = phi) to ~1e-12 -- with its own alpha,
+ * beta, residual and stop test ||r_b|| < tol ||phi_b||; a column that has
+ * stopped costs nothing more, and its x, iteration count and residual are
+ * those of the moment it stopped. A column's result does not depend on K, on
+ * its position in the batch or on the other columns: bitwise the same alone
+ * and in any batch.
+ * Layout: K columns, contiguous, column b at offset b * 2*Nx*Nt complex, each
+ * laid out as sm_cg_dev's field (plane mu0, then plane mu1). x must not alias
+ * phi. res[b] reports column b exactly as sm_cg_result reports a lone solve.
+ * Returns SM_OK also when some columns reach max_iter (res[b].converged says
+ * so); SM_ERR_ARG for K < 1, K > sm_cg_batch_max(), a null pointer, and on
+ * sharded, host-staged, loopback and peer contexts (version 1 is one shard);
+ * SM_ERR_STATE before a gauge upload; SM_ERR_HIP when the workspace cannot be
+ * allocated (sm_last_error() names the bytes asked for; the context stays
+ * usable).
+ * Always fp64: sm_cg_precision and sm_eo_cg_precision do not reach it.
+ * Traffic per site and column: 224 B per iteration (read d_{j-1}, d_{j-2},
+ * Ad_{j-1}: 96; write d_j, Ad_j: 64; x read + written every other pass: 32
+ * mean; links 32, from cache after the first column). Workspace, allocated at
+ * the first batched solve, regrown when a later call has a larger K and freed
+ * by sm_destroy: three direction and two Ad buffers, 160 B per site and
+ * column (the host-pointer entry and the correlator stage phi and x on the
+ * device: 64 B more), plus 48 B of partial sums per column and (60 t-columns
+ * x G rows) with G = 1 below Nx = 512, 8 from there, and one scalar block per
+ * column. It shares no buffer or state with sm_cg_begin / iterate / finish,
+ * sm_cg_dev, the mixed or the even-odd solvers, and keeps nothing derived
+ * from the gauge field: an upload or an HMC trajectory between two batched
+ * solves needs no call. Synchronous. */
+int sm_cg_batch_max(void);   /* largest K accepted (64) */
+int sm_cg_batch_dev(sm_ctx *ctx, int K, const double *phi, double *x, double m0, double tol, int max_iter,
+                    sm_cg_result *res /* K */);
+/* The same with host pointers (K columns in the layout above). */
+int sm_cg_batch(sm_ctx *ctx, int K, const double *phi, double *x, double m0, double tol, int max_iter,
+                sm_cg_result *res /* K */);
+/* Pion correlator from nsrc point sources on the current gauge field. For
+ * source s and spin a in {0, 1}: phi = the unit vector at site (src_x[s],
+ * src_t[s]) of plane a (built on the device), y_a = (D D^dag)^-1 phi in ONE
+ * batched solve of 2 nsrc columns (2 nsrc <= sm_cg_batch_max()), S_a =
+ * D^dag y_a = D^-1 phi, and
+ *   C[s*Nt + t] = sum_x sum_a (|S_a,0(x,t)|^2 + |S_a,1(x,t)|^2) = sum_x tr S S^dag,
+ * the pion by gamma5-hermiticity. t is the absolute time coordinate (the
+ * caller shifts by src_t[s]). The sums run in a fixed order without atomics:
+ * repeated calls agree bitwise. C: nsrc*Nt doubles on the host; res
+ * (nullable): the 2 nsrc solves, column 2 s + a. SM_ERR_ARG for nsrc < 1,
+ * 2 nsrc above the cap or a coordinate out of range; otherwise as
+ * sm_cg_batch. Memory: 224 B per site and column while it runs. */
+int sm_pion_correlator(sm_ctx *ctx, double m0, double tol, int max_iter, int nsrc, const int *src_x,
+                       const int *src_t, double *C /* nsrc*Nt, host */, sm_cg_result *res /* 2*nsrc, nullable */);
+
 /* Gather the sharded gauge field to shard 0 (SaveConf's MPI_Gatherv,
  * src/gauge_conf.cpp:378-396): U0/U1 on shard 0 receive the global
  * Nx x Nt field (n = x*Nt + t); other shards may pass NULL. RCCL transport

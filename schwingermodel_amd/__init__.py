@@ -158,6 +158,40 @@ class Lattice:
         check(lib.sm_eo_cg_mixed_last(self.ctx, ctypes.byref(info)))
         return info
 
+    def cg_batch(self, phi, m0, tol=None, max_iter=None):
+        """Solve D D^dagger x_b = phi_b for K right-hand sides on the context's
+        current gauge field in one batched solve (sm_cg_batch; no implicit
+        upload). phi: complex128 of shape (K, 2, V), column b = (plane mu0,
+        plane mu1). Returns (x, [CGResult] * K); always fp64, each column with
+        its own stop test and iteration count."""
+        if not isinstance(phi, np.ndarray) or phi.dtype != np.complex128:
+            raise TypeError("cg_batch: phi must be a complex128 numpy array")
+        if phi.ndim != 3 or phi.shape[1:] != (2, self.V) or phi.shape[0] < 1:
+            raise ValueError(f"cg_batch: phi has shape {phi.shape}, expected (K, 2, {self.V})")
+        K = phi.shape[0]
+        phi = np.ascontiguousarray(phi)
+        x = np.empty_like(phi)
+        res = (CGResult * K)()
+        check(lib.sm_cg_batch(self.ctx, K, _vp(phi), _vp(x), float(m0), float(CG.tol if tol is None else tol),
+                              int(CG.max_iter if max_iter is None else max_iter), res))
+        return x, list(res)
+
+    def pion_correlator(self, m0, sources, tol=None, max_iter=None):
+        """Pion correlator from point sources on the context's current gauge
+        field (sm_pion_correlator; no implicit upload). sources: a list of
+        (x, t). Returns (C, results): C[s, t] = sum_x tr S S^dag at absolute
+        time t for source s, results = the 2 * len(sources) solves (column
+        2 s + spin)."""
+        src = [(int(x), int(t)) for x, t in sources]
+        n = len(src)
+        sx = (ctypes.c_int * max(n, 1))(*[s[0] for s in src])
+        st = (ctypes.c_int * max(n, 1))(*[s[1] for s in src])
+        C = np.zeros((max(n, 1), self.Wt))
+        res = (CGResult * max(2 * n, 1))()
+        check(lib.sm_pion_correlator(self.ctx, float(m0), float(CG.tol if tol is None else tol),
+                                     int(CG.max_iter if max_iter is None else max_iter), n, sx, st, _vp(C), res))
+        return C, list(res)
+
     def close(self):
         if self.ctx:
             lib.sm_destroy(self.ctx)

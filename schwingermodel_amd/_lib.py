@@ -143,6 +143,12 @@ def _load():
         "sm_gather_gauge": ([vp, vp, vp], ci),
         "sm_eo_dhat": ([vp, ci, vp, vp, vp, vp, cd], ci),
         "sm_eo_cg": ([vp, vp, vp, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
+        # batched multi-source CG, pion correlator
+        "sm_cg_batch_max": ([], ci),
+        "sm_cg_batch_dev": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
+        "sm_cg_batch": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
+        "sm_pion_correlator": ([vp, cd, cd, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp,
+                                ctypes.POINTER(CGResult)], ci),
     }
     for name, (args, res) in sig.items():
         if ab_override and not hasattr(lib, name):

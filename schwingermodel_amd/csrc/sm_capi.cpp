@@ -260,6 +260,7 @@ int sm_comm_unique_id(void *id_out, int id_bytes) {
 //   probe_min_mib=N     smallest field (MiB) whose context runs the probe
 //   link_angles=0|1     recompute-Ad pass reads the links as one-double codes
 //   ra_xchunk=N         recompute-Ad pass: N rows per tile (with ra_xbal=1: ceil(Nx/N) balanced chunks)
+//   batch_tiles=N       batched CG (sm_cgbatch.cpp): tiles per launch the tile height aims at
 //   kernel_events=0|1   t-shard CG pass: hand-offs between the streams on events
 //                       recorded by the launches themselves (1, the default) or markers
 //   bt=64|128|256       Dirac apply t-columns per block
@@ -327,6 +328,9 @@ static int apply_test_opts(sm_ctx *c) {
             if (iv < 2 || iv > c->g.Nx) return fail(SM_ERR_ARG, "SM_TEST_OPTS: ra_xchunk must be 2..Nx");
             c->racfg.xchunk = iv;
             c->racfg.XB = (c->g.Nx + iv - 1) / iv;
+        } else if (k == "batch_tiles") {  // batched CG: tiles per launch the tile height aims at
+            if (iv < 1) return fail(SM_ERR_ARG, "SM_TEST_OPTS: batch_tiles must be >= 1");
+            c->bt_tiles = iv;
         } else if (k == "ra_xbal") {
             c->racfg.xbal = iv ? 1 : 0;
         } else if (k == "ra_remap") {
@@ -615,6 +619,7 @@ int sm_destroy(sm_ctx *c) {
     c->Uang = nullptr;
     cg_mixed_free(c);
     eo_cg_mixed_free(c);
+    cg_batch_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};

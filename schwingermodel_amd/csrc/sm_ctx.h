@@ -227,6 +227,21 @@ struct sm_ctx {
     double2 *eomp_partials = nullptr;
     sm::MPScalars *eomp_sc = nullptr, *eomp_h_sc = nullptr;  // device, pinned host mirror
     sm_cg_mixed_info eomp_info{};   // the last even-odd solve
+    // batched multi-source CG (sm_cgbatch.cpp; one shard, always fp64): its own
+    // directions, Ad buffers, scalars and partials for bt_K columns, from the
+    // first batched solve on and regrown for a larger K. Reads c->U at every
+    // call; keeps nothing that depends on the gauge field.
+    int bt_K = 0;                   // columns the workspace holds
+    int bt_tiles = 0;               // test option batch_tiles=N: tiles per launch aimed at (0: kBatchTargetTiles)
+    double2 *bt_d[3] = {};          // d_i in bt_d[i mod 3], K x 2V complex each
+    double2 *bt_a[2] = {};          // Ad by pass parity
+    double2 *bt_partials = nullptr; // K x CGBatchCfg::pstride
+    sm::CGScalars *bt_sc = nullptr, *bt_h_sc = nullptr;  // K each: device, pinned host mirror
+    // pion correlator: sources / solutions (bt_pion_K columns), source coordinates, C
+    int bt_pion_K = 0;
+    double2 *bt_phi = nullptr, *bt_x = nullptr;
+    int *bt_src = nullptr;          // 2 x kBatchMax / 2 ints
+    double *bt_C = nullptr;         // kBatchMax / 2 x Wt
 
     double2 *field(int i) { return fields[i]; }
 };
@@ -331,6 +346,7 @@ int placement_probe_default();            // candidates per buffer for new conte
 int cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 int cg_dev_mixed(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 void cg_mixed_free(sm_ctx *c);
+void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's workspaces (sm_cgbatch.cpp)
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

@@ -255,6 +255,42 @@ void launch_mp_fold(hipStream_t s, const Geometry &g, double2 *x, float2 *y, con
 void launch_mp_add(hipStream_t s, long n, double2 *x, const double2 *e);
 void launch_mp_zero(hipStream_t s, long n, float2 *y);
 
+// ---- batched multi-source CG and the pion correlator (sm_cgbatch.hip; driver sm_cgbatch.cpp) ----
+// K columns, 2V complex apart, on one gauge field; one shard. A tile is one
+// wave: 60 owned t-columns x xchunk rows. Partials are kept per granule of G
+// rows (G from the lattice alone), so a column's sums do not depend on K.
+constexpr int kBatchMax = 64;            // sm_cg_batch_max()
+constexpr int kBatchRedMaxSlots = 512;   // redundant scalars up to this many partial slots per column
+// tiles per launch the tile height aims at: one resident round (256 CUs x 4 SIMDs x 2 waves at the
+// pass's 210-220 VGPRs); measured best of 1024..16384 at 64^2 and 256^2
+constexpr int kBatchTargetTiles = 2048;
+struct CGBatchCfg {
+    int NWT;        // wave tiles along t
+    int G, NG;      // rows per granule, granules per column of tiles
+    int P;          // partial slots per column (NWT * NG), 3 complex each
+    int red;        // 1: redundant scalars (every tile sums its column's previous partials)
+    int xchunk;     // rows per tile (a multiple of G)
+    int NCH;        // tiles along x
+    int NB0;        // blocks per column of the start kernel
+    long pstride;   // complex per column in the partials buffer
+};
+CGBatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles = 0);
+// x = phi, T = D^dag phi, d0 = r_0 = phi - D T, and the columns' scalars (tol, max_iter, S_-1)
+void launch_cg_batch_init(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *phi, double2 *x,
+                          double2 *T, double2 *d0, const double2 *U, double mass, double tol, int max_iter,
+                          double2 *partials, CGScalars *sc);
+// pass j of every column that is not done (and, without redundant scalars, its scalar step)
+void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *dold,
+                          const double2 *rold, const double2 *aold, double2 *dnew, double2 *anew, double2 *x,
+                          const double2 *U, double mass, long pass, CGScalars *sc, double2 *partials);
+// redundant scalars: the last issued pass's state into sc for the host
+void launch_cg_batch_flush(hipStream_t s, const CGBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
+                           long pass);
+void launch_cg_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
+                              const double2 *d1, const double2 *d2, const CGScalars *sc);
+void launch_point_sources(hipStream_t s, const Geometry &g, int K, const int *sx, const int *st, double2 *phi);
+void launch_pion_slices(hipStream_t s, const Geometry &g, int nsrc, const double2 *S, double *C);
+
 // ---- gauge field / molecular dynamics (sm_gauge.hip) ----
 // fU: the 2-deep U faces (nshard > 1; ignored for one shard, which wraps).
 int gauge_reduce_blocks(const Geometry &g);
