@@ -552,6 +552,66 @@ int sm_cg_batch(sm_ctx *ctx, int K, const double *phi, double *x, double m0, dou
 int sm_pion_correlator(sm_ctx *ctx, double m0, double tol, int max_iter, int nsrc, const int *src_x,
                        const int *src_t, double *C /* nsrc*Nt, host */, sm_cg_result *res /* 2*nsrc, nullable */);
 
+/* ==== replica ensemble: R independent HMC chains, one launch per step ========
+ * R <= sm_ens_max() gauge fields in one context, evolved in lockstep: every CG
+ * iteration and every molecular-dynamics kernel is ONE launch for all replicas
+ * (schwingermodel_amd/csrc/sm_ens.cpp). A lone chain on a 16^2-256^2 lattice
+ * is bound by launch latency (11-12 us per CG iteration whatever the lattice);
+ * R chains -- more statistics, or one chain per (beta, m0) point of a scan --
+ * share that cost. Replica r has its own m0, beta, tau and seed; md_steps,
+ * cg_tol and cg_max_iter are common (the replicas share every launch) and
+ * even_odd must be 0: anything else is SM_ERR_ARG naming the field.
+ * sm_ens_hmc_trajectory is HMC::HMC_Update (src/hmc.cpp:151-178) for every
+ * replica at once: the draws, phi = D chi, H_old (one batched solve of R
+ * columns, column r on replica r's links and mass), the leapfrog with the
+ * reference's loop bound (md_steps - 1 batched force solves), H_new, and a
+ * Metropolis step per replica with r = uniform(seed_r, traj). out[r] reports
+ * replica r as sm_hmc_result reports a lone chain; cg_iterations counts the
+ * replica's own column, not the slowest one.
+ * What a replica computes depends on its own field, parameters and seed only:
+ * bitwise the same alone (R = 1), at any position of any ensemble, whatever
+ * the other replicas hold. Its draws are those of a lone chain with p[r].seed
+ * (sm_traj_seed(seed, traj); the hot start of sm_ens_hmc_run from
+ * sm_traj_seed(seed, ~0), as sm_hmc_run). sp and gauge_action are bitwise what
+ * sm_plaquette gives a lone context holding the same field; quantities
+ * downstream of a CG solve agree with the lone chain to the solvers' rounding
+ * (the batched CG sums in another order than sm_cg_dev's), so a lone chain and
+ * a replica started alike drift apart like two decompositions of one chain.
+ * A rejected replica gets its previous field back bitwise (a device copy of
+ * that replica only). Always fp64: sm_cg_precision and sm_eo_cg_precision do
+ * not reach it. The ensemble owns its fields (U and its backup, momenta,
+ * force, chi, phi, x: 192 B per site and replica) and its solver workspace
+ * (160 B per site and replica); the context's gauge field, sm_cg_dev,
+ * sm_cg_batch, the stepwise solver and their buffers are untouched by any
+ * ensemble call. It works on the context's stream; destroy it before the
+ * context. SM_ERR_ARG on sharded, host-staged, loopback and peer contexts, for
+ * R < 1 or R > sm_ens_max(), r out of range and null pointers; SM_ERR_STATE
+ * while some replica has no gauge field; SM_ERR_HIP (sm_last_error() names the
+ * bytes asked for) when an allocation fails, after which the context stays
+ * usable. Synchronous.
+ * Not in this version: t-sharded ensembles, the even-odd action, mixed
+ * precision, the sm_hmc program. */
+typedef struct sm_ens sm_ens;
+int sm_ens_max(void);   /* = sm_cg_batch_max() */
+int sm_ens_create(sm_ctx *ctx, int R, sm_ens **out);   /* allocates all fields */
+int sm_ens_destroy(sm_ens *e);
+int sm_ens_size(const sm_ens *e, int *R);
+/* Replica r's field, as sm_upload_gauge / sm_download_gauge / sm_fill_gauge_dev */
+int sm_ens_upload_gauge(sm_ens *e, int r, const double *U0, const double *U1);
+int sm_ens_download_gauge(sm_ens *e, int r, double *U0, double *U1);
+int sm_ens_fill_gauge(sm_ens *e, int r, uint64_t seed, double sigma);
+/* sp[r] = sum Re U_01, gauge_action[r] = beta[r] sum Re(1 - U_01) of replica r:
+ * one launch and one synchronisation for all R, bitwise sm_plaquette's values */
+int sm_ens_plaquette(sm_ens *e, const double *beta /* R */, double *sp /* R */, double *gauge_action /* R */);
+int sm_ens_hmc_trajectory(sm_ens *e, const sm_hmc_params *p /* R */, uint64_t traj, sm_hmc_result *out /* R */);
+/* sm_hmc_run per replica (the reference's statistics and acceptance
+ * definition; out[r].cg_link_bytes = 32). The series are R rows of Nmeas.
+ * save_prefix (nullable): after measurement i replica r's field goes to
+ * <save_prefix>_r<r>_<i>.ctxt in the 28-byte record format. */
+int sm_ens_hmc_run(sm_ens *e, const sm_hmc_params *p /* R */, int hot_start, uint64_t first_traj, int Ntherm,
+                   int Nmeas, int Nsteps, const char *save_prefix, sm_hmc_summary *out /* R */,
+                   double *sp_series /* R*Nmeas, nullable */, double *gs_series /* R*Nmeas, nullable */);
+
 /* Gather the sharded gauge field to shard 0 (SaveConf's MPI_Gatherv,
  * src/gauge_conf.cpp:378-396): U0/U1 on shard 0 receive the global
  * Nx x Nt field (n = x*Nt + t); other shards may pass NULL. RCCL transport

@@ -27,7 +27,7 @@ import numpy as np
 
 from ._lib import CGMixedInfo, CGResult, HamiltonianTerms, HMCParams, HMCResult, HMCSummary, SMError, check, lib
 
-__all__ = ["spinor", "re_field", "c_double", "I_number", "CG", "init", "lattice", "Lattice",
+__all__ = ["spinor", "re_field", "c_double", "I_number", "CG", "init", "lattice", "Lattice", "Ensemble",
            "D_phi", "D_dagger_phi", "D_D_dagger_phi", "phi_dag_partialD_phi",
            "conjugate_gradient", "dot", "SMError", "CGResult", "lib", "check"]
 
@@ -192,6 +192,11 @@ class Lattice:
                                      int(CG.max_iter if max_iter is None else max_iter), n, sx, st, _vp(C), res))
         return C, list(res)
 
+    def ensemble(self, R):
+        """An Ensemble of R independent HMC chains on this lattice, evolved in
+        lockstep with one launch per step for all of them (sm_ens_create)."""
+        return Ensemble(self, R)
+
     def close(self):
         if self.ctx:
             lib.sm_destroy(self.ctx)
@@ -213,6 +218,103 @@ class Lattice:
     def upload_gauge(self, U):
         self._check_field(U, "U")
         check(lib.sm_upload_gauge(self.ctx, _vp(U.mu0), _vp(U.mu1)))
+
+
+class Ensemble:
+    """R replicas of a Lattice's gauge field, each with its own m0, beta, tau
+    and seed, evolved by HMC in lockstep (owns an sm_ens; include/sm_hip.h
+    "replica ensemble"). Close it before its Lattice. Gauge fields are
+    complex128 arrays of shape (2, V): plane U_t, then plane U_x."""
+
+    def __init__(self, lattice, R):
+        if not isinstance(R, int) or isinstance(R, bool) or R < 1:
+            raise ValueError(f"ensemble: R = {R!r}, expected an integer >= 1")
+        self.lattice, self.R, self.V = lattice, R, lattice.V
+        h = ctypes.c_void_p()
+        check(lib.sm_ens_create(lattice.ctx, R, ctypes.byref(h)))
+        self.ens = h
+
+    def close(self):
+        if self.ens:
+            lib.sm_ens_destroy(self.ens)
+            self.ens = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _replica(self, r):
+        if not isinstance(r, (int, np.integer)) or not 0 <= r < self.R:
+            raise ValueError(f"ensemble: replica {r!r} outside 0..{self.R - 1}")
+        return int(r)
+
+    def _params(self, params):
+        """The R parameter sets as a ctypes array, checked for lockstep."""
+        params = list(params)
+        if len(params) != self.R:
+            raise ValueError(f"ensemble: {len(params)} parameter sets for {self.R} replicas")
+        for p in params:
+            if not isinstance(p, HMCParams):
+                raise TypeError("ensemble: params must be HMCParams")
+            for name in ("md_steps", "cg_tol", "cg_max_iter"):
+                if getattr(p, name) != getattr(params[0], name):
+                    raise ValueError(f"ensemble: {name} must be the same for every replica")
+            if p.even_odd != 0:
+                raise ValueError("ensemble: even_odd must be 0")
+        return (HMCParams * self.R)(*params)
+
+    def upload_gauge(self, r, U):
+        r = self._replica(r)
+        if not isinstance(U, np.ndarray) or U.dtype != np.complex128:
+            raise TypeError("ensemble: U must be a complex128 numpy array")
+        if U.shape != (2, self.V):
+            raise ValueError(f"ensemble: U has shape {U.shape}, expected (2, {self.V})")
+        U = np.ascontiguousarray(U)
+        check(lib.sm_ens_upload_gauge(self.ens, r, _vp(U[0]), _vp(U[1])))
+
+    def download_gauge(self, r):
+        r = self._replica(r)
+        U = np.empty((2, self.V), dtype=np.complex128)
+        check(lib.sm_ens_download_gauge(self.ens, r, _vp(U[0]), _vp(U[1])))
+        return U
+
+    def fill_gauge(self, r, seed, sigma):
+        """Replica r's field drawn on the device as sm_fill_gauge_dev draws it
+        (sigma < 0: uniform angles, the hot start)."""
+        r = self._replica(r)
+        check(lib.sm_ens_fill_gauge(self.ens, r, int(seed), float(sigma)))
+
+    def plaquette(self, betas):
+        """(sp, gauge_action): arrays of R, sum Re U_01 and beta_r sum Re(1 - U_01)."""
+        b = np.ascontiguousarray(betas, dtype=np.float64)
+        if b.shape != (self.R,):
+            raise ValueError(f"ensemble: {b.size} betas for {self.R} replicas")
+        sp, act = np.empty(self.R), np.empty(self.R)
+        check(lib.sm_ens_plaquette(self.ens, _vp(b), _vp(sp), _vp(act)))
+        return sp, act
+
+    def trajectory(self, params, traj):
+        """One HMC update of every replica (sm_ens_hmc_trajectory): params is a
+        list of R HMCParams; returns R HMCResult."""
+        p = self._params(params)
+        out = (HMCResult * self.R)()
+        check(lib.sm_ens_hmc_trajectory(self.ens, p, int(traj), out))
+        return list(out)
+
+    def run(self, params, Ntherm, Nmeas, Nsteps, hot_start=True, first_traj=0, save_prefix=None):
+        """sm_ens_hmc_run: returns (R HMCSummary, sp, gs), the series of shape
+        (R, Nmeas). save_prefix: <save_prefix>_r<r>_<i>.ctxt after measurement i."""
+        p = self._params(params)
+        if Ntherm < 0 or Nmeas < 1 or Nsteps < 0:
+            raise ValueError(f"ensemble: Ntherm={Ntherm} Nmeas={Nmeas} Nsteps={Nsteps}")
+        out = (HMCSummary * self.R)()
+        sp, gs = np.empty((self.R, Nmeas)), np.empty((self.R, Nmeas))
+        prefix = None if save_prefix is None else str(save_prefix).encode()
+        check(lib.sm_ens_hmc_run(self.ens, p, 1 if hot_start else 0, int(first_traj), int(Ntherm), int(Nmeas),
+                                 int(Nsteps), prefix, out, _vp(sp), _vp(gs)))
+        return list(out), sp, gs
 
 
 _LATTICE = None

@@ -149,6 +149,18 @@ def _load():
         "sm_cg_batch": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
         "sm_pion_correlator": ([vp, cd, cd, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp,
                                 ctypes.POINTER(CGResult)], ci),
+        # replica ensemble: R HMC chains in lockstep
+        "sm_ens_max": ([], ci),
+        "sm_ens_create": ([vp, ci, ctypes.POINTER(vp)], ci),
+        "sm_ens_destroy": ([vp], ci),
+        "sm_ens_size": ([vp, ctypes.POINTER(ci)], ci),
+        "sm_ens_upload_gauge": ([vp, ci, vp, vp], ci),
+        "sm_ens_download_gauge": ([vp, ci, vp, vp], ci),
+        "sm_ens_fill_gauge": ([vp, ci, u64, cd], ci),
+        "sm_ens_plaquette": ([vp, vp, vp, vp], ci),
+        "sm_ens_hmc_trajectory": ([vp, ctypes.POINTER(HMCParams), u64, ctypes.POINTER(HMCResult)], ci),
+        "sm_ens_hmc_run": ([vp, ctypes.POINTER(HMCParams), ci, u64, ci, ci, ci, ctypes.c_char_p,
+                            ctypes.POINTER(HMCSummary), vp, vp], ci),
     }
     for name, (args, res) in sig.items():
         if ab_override and not hasattr(lib, name):

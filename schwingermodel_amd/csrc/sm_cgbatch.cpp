@@ -33,25 +33,25 @@ static void free_dev(void *p) {
     if (p) (void)hipFree(p);
 }
 
-static void free_solver_ws(sm_ctx *c) {
-    for (double2 *&d : c->bt_d) {
+void cg_batch_ws_free(CGBatchWs &w) {
+    for (double2 *&d : w.d) {
         free_dev(d);
         d = nullptr;
     }
-    for (double2 *&a : c->bt_a) {
+    for (double2 *&a : w.a) {
         free_dev(a);
         a = nullptr;
     }
-    free_dev(c->bt_partials);
-    free_dev(c->bt_sc);
-    if (c->bt_h_sc) (void)hipHostFree(c->bt_h_sc);
-    c->bt_partials = nullptr;
-    c->bt_sc = c->bt_h_sc = nullptr;
-    c->bt_K = 0;
+    free_dev(w.partials);
+    free_dev(w.sc);
+    if (w.h_sc) (void)hipHostFree(w.h_sc);
+    w.partials = nullptr;
+    w.sc = w.h_sc = nullptr;
+    w.K = 0;
 }
 
 void cg_batch_free(sm_ctx *c) {
-    free_solver_ws(c);
+    cg_batch_ws_free(c->bt);
     free_dev(c->bt_phi);
     free_dev(c->bt_x);
     free_dev(c->bt_src);
@@ -72,37 +72,42 @@ static int alloc_dev(void **p, size_t bytes, const char *what) {
 }
 
 // The solver's workspace for K columns: three d buffers, two Ad buffers
-// (K x 32 V bytes each), partials and scalars. Kept while K fits, regrown else.
-static int batch_ready(sm_ctx *c, int K) {
-    if (c->bt_K >= K) return SM_OK;
+// (K x 32 V bytes each), partials and scalars.
+int cg_batch_ws_alloc(sm_ctx *c, CGBatchWs &w, int K) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_solver_ws(c);
+    cg_batch_ws_free(w);
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
     const CGBatchCfg cfg = cg_batch_config(c->g, K, c->bt_tiles);  // pstride does not depend on K
     const size_t pb = sizeof(double2) * (size_t)cfg.pstride * (size_t)K;
     int rc = SM_OK;
-    for (double2 *&d : c->bt_d)
+    for (double2 *&d : w.d)
         if (rc == SM_OK) rc = alloc_dev((void **)&d, fb, "direction buffer");
-    for (double2 *&a : c->bt_a)
+    for (double2 *&a : w.a)
         if (rc == SM_OK) rc = alloc_dev((void **)&a, fb, "Ad buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->bt_partials, pb, "partials");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->bt_sc, sizeof(CGScalars) * (size_t)K, "scalars");
-    if (rc == SM_OK && hipHostMalloc((void **)&c->bt_h_sc, sizeof(CGScalars) * (size_t)K) != hipSuccess) {
-        c->bt_h_sc = nullptr;
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, "partials");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sizeof(CGScalars) * (size_t)K, "scalars");
+    if (rc == SM_OK && hipHostMalloc((void **)&w.h_sc, sizeof(CGScalars) * (size_t)K) != hipSuccess) {
+        w.h_sc = nullptr;
         (void)hipGetLastError();
         rc = fail(SM_ERR_HIP, "batched CG: allocating %zu pinned bytes (scalars) failed", sizeof(CGScalars) * (size_t)K);
     }
     if (rc != SM_OK) {
-        free_solver_ws(c);
+        cg_batch_ws_free(w);
         return rc;
     }
     // every buffer is read by halo lanes / rows before its first write: defined values
-    for (double2 *d : c->bt_d) HIP_TRY(hipMemsetAsync(d, 0, fb, c->stream));
-    for (double2 *a : c->bt_a) HIP_TRY(hipMemsetAsync(a, 0, fb, c->stream));
-    HIP_TRY(hipMemsetAsync(c->bt_partials, 0, pb, c->stream));
-    HIP_TRY(hipMemsetAsync(c->bt_sc, 0, sizeof(CGScalars) * (size_t)K, c->stream));
-    c->bt_K = K;
+    for (double2 *d : w.d) HIP_TRY(hipMemsetAsync(d, 0, fb, c->stream));
+    for (double2 *a : w.a) HIP_TRY(hipMemsetAsync(a, 0, fb, c->stream));
+    HIP_TRY(hipMemsetAsync(w.partials, 0, pb, c->stream));
+    HIP_TRY(hipMemsetAsync(w.sc, 0, sizeof(CGScalars) * (size_t)K, c->stream));
+    w.K = K;
     return SM_OK;
+}
+
+// The context's own workspace: kept while K fits, regrown else.
+static int batch_ready(sm_ctx *c, int K) {
+    HIP_TRY(hipSetDevice(c->device));
+    return c->bt.K >= K ? SM_OK : cg_batch_ws_alloc(c, c->bt, K);
 }
 
 // Device staging for the host-pointer entry and the correlator: phi and x, K columns.
@@ -133,32 +138,29 @@ static int batch_check(sm_ctx *c, int K) {
     return SM_OK;
 }
 
-static int cg_batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
-                          sm_cg_result *res) {
+int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
+                   double tol, int max_iter, sm_cg_result *res) {
     HIP_TRY(hipSetDevice(c->device));
-    TRY(batch_ready(c, K));
     const CGBatchCfg cfg = cg_batch_config(c->g, K, c->bt_tiles);
-    const double mass = m0 + 2;
-    auto dbuf = [&](long i) { return c->bt_d[((i % 3) + 3) % 3]; };
+    auto dbuf = [&](long i) { return w.d[((i % 3) + 3) % 3]; };
     // d_0 goes where pass 0 expects d_{-1}: it copies it to dbuf(0) while forming Ad_0
-    launch_cg_batch_init(c->stream, c->g, cfg, K, phi, x, c->bt_a[0], dbuf(-1), c->U, mass, tol, max_iter,
-                         c->bt_partials, c->bt_sc);
+    launch_cg_batch_init(c->stream, c->g, cfg, K, phi, x, w.a[0], dbuf(-1), l, tol, max_iter, w.partials, w.sc);
     HIP_TRY(hipGetLastError());
     const long passes = (long)max_iter + 1;  // pass 0 forms Ad_0; a column stops itself at k == max_iter
     std::vector<CgChunker> plan((size_t)K);
     long issued = 0;
     int chunk = 4;
-    const CGScalars *h = c->bt_h_sc;
+    const CGScalars *h = w.h_sc;
     for (;;) {
         const long nb = passes - issued < chunk ? passes - issued : chunk;
         for (long i = 0; i < nb; ++i, ++issued) {
             const long j = issued;
-            launch_cg_batch_pass(c->stream, c->g, cfg, K, dbuf(j - 1), dbuf(j - 2), c->bt_a[(j + 1) & 1], dbuf(j),
-                                 c->bt_a[j & 1], x, c->U, mass, j, c->bt_sc, c->bt_partials);
+            launch_cg_batch_pass(c->stream, c->g, cfg, K, dbuf(j - 1), dbuf(j - 2), w.a[(j + 1) & 1], dbuf(j),
+                                 w.a[j & 1], x, l, j, w.sc, w.partials);
         }
-        if (nb > 0) launch_cg_batch_flush(c->stream, cfg, K, c->bt_partials, c->bt_sc, issued - 1);
+        if (nb > 0) launch_cg_batch_flush(c->stream, cfg, K, w.partials, w.sc, issued - 1);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->bt_h_sc, c->bt_sc, sizeof(CGScalars) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(w.h_sc, w.sc, sizeof(CGScalars) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         int open = 0, wish = 2;
         for (int b = 0; b < K; ++b) {
@@ -171,7 +173,7 @@ static int cg_batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, doub
         if (!open || issued >= passes) break;
         chunk = wish;
     }
-    launch_cg_batch_finish_x(c->stream, c->g, K, x, c->bt_d[0], c->bt_d[1], c->bt_d[2], c->bt_sc);
+    launch_cg_batch_finish_x(c->stream, c->g, K, x, w.d[0], w.d[1], w.d[2], w.sc);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
     for (int b = 0; b < K; ++b) {
@@ -198,7 +200,9 @@ int sm_cg_batch_dev(sm_ctx *c, int K, const double *phi, double *x, double m0, d
     if ((const double *)x == phi) return fail(SM_ERR_ARG, "batched CG: x must not alias phi");
     if (max_iter < 0) return fail(SM_ERR_ARG, "batched CG: max_iter < 0");
     TRY(check_ready(c));
-    return cg_batch_solve(c, K, (const double2 *)phi, (double2 *)x, m0, tol, max_iter, res);
+    TRY(batch_ready(c, K));
+    return cg_batch_solve(c, c->bt, K, (const double2 *)phi, (double2 *)x, shared_links(c->U, m0 + 2), tol, max_iter,
+                          res);
 }
 
 int sm_cg_batch(sm_ctx *c, int K, const double *phi, double *x, double m0, double tol, int max_iter,
@@ -211,7 +215,8 @@ int sm_cg_batch(sm_ctx *c, int K, const double *phi, double *x, double m0, doubl
     TRY(staging_ready(c, K));
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
     HIP_TRY(hipMemcpyAsync(c->bt_phi, phi, fb, hipMemcpyHostToDevice, c->stream));
-    TRY(cg_batch_solve(c, K, c->bt_phi, c->bt_x, m0, tol, max_iter, res));
+    TRY(batch_ready(c, K));
+    TRY(cg_batch_solve(c, c->bt, K, c->bt_phi, c->bt_x, shared_links(c->U, m0 + 2), tol, max_iter, res));
     HIP_TRY(hipMemcpyAsync(x, c->bt_x, fb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SM_OK;
@@ -245,9 +250,10 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
     HIP_TRY(hipGetLastError());
     std::vector<sm_cg_result> own((size_t)K);
     sm_cg_result *r = res ? res : own.data();
-    TRY(cg_batch_solve(c, K, c->bt_phi, c->bt_x, m0, tol, max_iter, r));
+    TRY(batch_ready(c, K));
+    TRY(cg_batch_solve(c, c->bt, K, c->bt_phi, c->bt_x, shared_links(c->U, m0 + 2), tol, max_iter, r));
     // S_a = D^dag y_a (the existing apply) into the solver's first Ad buffer, free after the solve
-    double2 *S = c->bt_a[0];
+    double2 *S = c->bt.a[0];
     const long n = 2 * c->g.V;
     for (int k = 0; k < K; ++k) TRY(apply(c, c->bt_x + k * n, S + k * n, m0 + 2, 1, nullptr, nullptr, nullptr));
     launch_pion_slices(c->stream, c->g, nsrc, S, c->bt_C);

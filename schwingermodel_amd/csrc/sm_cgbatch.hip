@@ -18,6 +18,14 @@
 // along x. No LDS, no barrier. The grid is K x NWT x NCH tiles, column-major
 // (all tiles of column 0, then column 1, ...).
 //
+// Links. Column b reads its links at U + b * ustride and uses its own mass
+// (BatchLinks, sm_internal.h): both come from scalar loads at the head of the
+// block and stay in SGPRs, no row reads them again. ustride = 0 with one mass
+// is the shared field of sm_cg_batch and the correlator (the arithmetic it had
+// before per-column links existed); a replica ensemble (sm_ens.cpp) gives
+// every column its own field and mass. Neither enters another column's
+// arithmetic.
+//
 // A column's sums must not depend on K, yet the tile height should: few
 // columns want one row per tile (parallelism), many columns want taller tiles
 // (4 halo rows are recomputed per tile). So partials are kept per GRANULE of G
@@ -49,7 +57,9 @@ struct CGBArgs {
     const double2 *dold, *rold, *aold;  // d_{j-1}, d_{j-2}, Ad_{j-1}: K columns, 2V complex apart
     double2 *dnew, *anew;               // d_j, Ad_j
     double2 *x;
-    const double2 *U;
+    const double2 *U;                   // column b's links at U + b * ustride (0: one field for all)
+    long ustride;
+    const double *massv;                // column b's mass (null: `mass` for all)
     CGScalars *sc;                      // K
     double2 *partials;                  // this pass's: column b at + b * pstride, 3 per slot
     const double2 *prev;                // RED: pass j-1's
@@ -74,6 +84,9 @@ __global__ void __launch_bounds__(64) cg_batch_kernel(CGBArgs a) {
     const int g = w % a.NWT, xc = w / a.NWT;
     const int lane = threadIdx.x;
     CGScalars *sc = a.sc + b;
+    // the column's mass and link base: block-uniform, scalar loads issued ahead of everything else
+    const double mass = a.massv ? a.massv[b] : a.mass;
+    const double2 *Ub = a.U + (long)b * a.ustride;
     const bool first = a.pass == 0;
     const double2 zz = make_double2(0.0, 0.0);
     double2 alpha = zz, beta = zz, alpha2 = zz, beta2 = zz;  // alpha_{j-1}, beta_{j-1}, alpha_{j-2}, beta_{j-2}
@@ -116,7 +129,7 @@ __global__ void __launch_bounds__(64) cg_batch_kernel(CGBArgs a) {
     const double sr0 = cw == Wt - 1 ? -1.0 : 1.0;  // SignR[2n], include/dirac_operator.h:53-55
     const double sl0 = cw == 0 ? -1.0 : 1.0;       // SignL[2n], :56-58
     const double2 *Sd = a.dold + col + cw, *Sr = a.rold + col + cw, *Sa = a.aold + col + cw;
-    const double2 *Su = a.U + cw;
+    const double2 *Su = Ub + cw;
     double2 *xb = a.x + col, *dn_ = a.dnew + col, *an_ = a.anew + col;
     auto wrap = [Nx](int x) { int q = x % Nx; return q < 0 ? q + Nx : q; };
     auto load = [&](int xr, RawB &R) {
@@ -163,7 +176,7 @@ __global__ void __launch_bounds__(64) cg_batch_kernel(CGBArgs a) {
         const Sp pm = shr(p), pp = shl(p);
         utm_out = dpp_shr1(ut);
         Sp o;
-        dirac_site<1>(a.mass, sr0, sl0, p.a, p.b, pp.a, pp.b, pxp.a, pxp.b, pm.a, pm.b, pxm.a, pxm.b, ut, ux,
+        dirac_site<1>(mass, sr0, sl0, p.a, p.b, pp.a, pp.b, pxp.a, pxp.b, pm.a, pm.b, pxm.a, pxm.b, ut, ux,
                       utm_out, uxm, o.a, o.b);
         return o;
     };
@@ -201,7 +214,7 @@ __global__ void __launch_bounds__(64) cg_batch_kernel(CGBArgs a) {
         const Sp Tn = ddag(dn, dc, d2, utn, uxn, uxc, utmn);
         const Sp Tm = shr(Tc), Tq = shl(Tc);
         Sp o;
-        dirac_site<0>(a.mass, sr0, sl0, Tc.a, Tc.b, Tq.a, Tq.b, Tn.a, Tn.b, Tm.a, Tm.b, Tp.a, Tp.b, utc, uxc, utmc,
+        dirac_site<0>(mass, sr0, sl0, Tc.a, Tc.b, Tq.a, Tq.b, Tn.a, Tn.b, Tm.a, Tm.b, Tp.a, Tp.b, utc, uxc, utmc,
                       uxp, o.a, o.b);
         if (own) {
             const long n = (long)x * Wt + c;
@@ -307,25 +320,30 @@ __device__ __forceinline__ void site_apply(const double2 *in, const double2 *U, 
                     in[nxm], in[nxm + V], U[n], U[n + V], U[ntm], U[nxm + V], o0, o1);
 }
 
-__global__ void __launch_bounds__(256) batch_ddag1_kernel(int K, int Nx, int Wt, long V, const double2 *phi,
-                                                          const double2 *U, double mass, double2 *T) {
-    const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)K * V) return;
-    const long b = i / V, n = i - b * V;
+// out_b = D in_b (DAG = 0) or D^dag in_b (1) on column b's links and mass;
+// grid NBA x K: block (q, b) takes sites q*256 + tid of column b
+template <int DAG>
+__global__ void __launch_bounds__(256) batch_apply_kernel(int Nx, int Wt, long V, const double2 *in, BatchLinks l,
+                                                          double2 *out) {
+    const long b = blockIdx.y, n = (long)blockIdx.x * 256 + threadIdx.x;
+    const double mass = l.massv ? l.massv[b] : l.mass;
+    if (n >= V) return;
     const int x = (int)(n / Wt), t = (int)(n - (long)x * Wt);
     double2 o0, o1;
-    site_apply<1>(phi + b * 2 * V, U, Nx, Wt, V, mass, x, t, o0, o1);
-    T[b * 2 * V + n] = o0;
-    T[b * 2 * V + n + V] = o1;
+    site_apply<DAG>(in + b * 2 * V, l.U + b * l.ustride, Nx, Wt, V, mass, x, t, o0, o1);
+    out[b * 2 * V + n] = o0;
+    out[b * 2 * V + n + V] = o1;
 }
 
 // grid K x NB0: block q of column b takes sites q*256 + tid, + NB0*256, ...
 __global__ void __launch_bounds__(256) batch_init_kernel(int NB0, int Nx, int Wt, long V, const double2 *phi,
-                                                         const double2 *T, const double2 *U, double mass, double2 *x,
-                                                         double2 *d0, double2 *partials, long pstride) {
+                                                         const double2 *T, BatchLinks l, double2 *x, double2 *d0,
+                                                         double2 *partials, long pstride) {
     __shared__ double2 sh[4];
     const int b = blockIdx.x / NB0, q = blockIdx.x - b * NB0;
     const long col = (long)b * 2 * V;
+    const double mass = l.massv ? l.massv[b] : l.mass;
+    const double2 *U = l.U + (long)b * l.ustride;
     double2 arr = make_double2(0.0, 0.0), app = make_double2(0.0, 0.0);
     for (long n = (long)q * 256 + threadIdx.x; n < V; n += (long)NB0 * 256) {
         const int xx = (int)(n / Wt), t = (int)(n - (long)xx * Wt);
@@ -423,25 +441,30 @@ CGBatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles) {
     return c;
 }
 
+void launch_batch_apply(hipStream_t s, const Geometry &g, int K, int dagger, const double2 *in, double2 *out,
+                        const BatchLinks &l) {
+    const dim3 grid((unsigned)((g.V + 255) / 256), (unsigned)K);
+    if (dagger) hipLaunchKernelGGL(batch_apply_kernel<1>, grid, dim3(256), 0, s, g.Nx, g.Wt, g.V, in, l, out);
+    else hipLaunchKernelGGL(batch_apply_kernel<0>, grid, dim3(256), 0, s, g.Nx, g.Wt, g.V, in, l, out);
+}
+
 void launch_cg_batch_init(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *phi, double2 *x,
-                          double2 *T, double2 *d0, const double2 *U, double mass, double tol, int max_iter,
-                          double2 *partials, CGScalars *sc) {
-    const long nthr = (long)K * g.V;
-    hipLaunchKernelGGL(batch_ddag1_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, K, g.Nx, g.Wt, g.V,
-                       phi, U, mass, T);
-    hipLaunchKernelGGL(batch_init_kernel, dim3(K * c.NB0), dim3(256), 0, s, c.NB0, g.Nx, g.Wt, g.V, phi, T, U, mass, x,
-                       d0, partials, c.pstride);
+                          double2 *T, double2 *d0, const BatchLinks &l, double tol, int max_iter, double2 *partials,
+                          CGScalars *sc) {
+    launch_batch_apply(s, g, K, 1, phi, T, l);
+    hipLaunchKernelGGL(batch_init_kernel, dim3(K * c.NB0), dim3(256), 0, s, c.NB0, g.Nx, g.Wt, g.V, phi, T, l, x, d0,
+                       partials, c.pstride);
     hipLaunchKernelGGL(batch_init_scalars_kernel, dim3(K), dim3(256), 0, s, c.NB0, partials, c.pstride, sc, tol,
                        max_iter);
 }
 
 void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *dold,
                           const double2 *rold, const double2 *aold, double2 *dnew, double2 *anew, double2 *x,
-                          const double2 *U, double mass, long pass, CGScalars *sc, double2 *partials) {
+                          const BatchLinks &l, long pass, CGScalars *sc, double2 *partials) {
     CGBArgs a;
     a.dold = dold; a.rold = rold; a.aold = aold;
     a.dnew = dnew; a.anew = anew;
-    a.x = x; a.U = U;
+    a.x = x; a.U = l.U; a.ustride = l.ustride; a.massv = l.massv;
     a.sc = sc;
     a.pstride = c.pstride;
     // redundant scalars: partials by pass parity, 3 P apart
@@ -450,7 +473,7 @@ void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const CGBatchCfg &c,
     a.pass = pass;
     a.V = g.V; a.Nx = g.Nx; a.Wt = g.Wt;
     a.xchunk = c.xchunk; a.G = c.G; a.NG = c.NG; a.NWT = c.NWT; a.NCH = c.NCH; a.P = c.P;
-    a.mass = mass;
+    a.mass = l.mass;
     const dim3 grid((unsigned)(K * c.NWT * c.NCH)), block(64);
     const bool xp = pass >= 2 && (pass & 1) == 0;
     if (c.red) {

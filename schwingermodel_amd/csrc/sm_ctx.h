@@ -48,6 +48,16 @@ int fail(int code, const char *fmt, ...);
 // six-launch path); F_AD2: the second Ad buffer of the stored-Ad pass (ping-pong with F_AD).
 enum { F_IN, F_OUT, F_TMP, F_X, F_R, F_D, F_D2, F_T, F_AD, F_PHI, F_L, F_RR, F_AD2, NFIELDS };
 
+// Workspace of a batched CG solve of up to K columns (sm_cgbatch.cpp): the
+// context owns one for sm_cg_batch, a replica ensemble (sm_ens.cpp) its own.
+struct CGBatchWs {
+    int K = 0;                      // columns it holds
+    double2 *d[3] = {};             // d_i in d[i mod 3], K x 2V complex each
+    double2 *a[2] = {};             // Ad by pass parity
+    double2 *partials = nullptr;    // K x CGBatchCfg::pstride
+    sm::CGScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
+};
+
 struct sm_ctx {
     int device = 0;
     int nshard = 1, shard = 0;
@@ -228,15 +238,11 @@ struct sm_ctx {
     sm::MPScalars *eomp_sc = nullptr, *eomp_h_sc = nullptr;  // device, pinned host mirror
     sm_cg_mixed_info eomp_info{};   // the last even-odd solve
     // batched multi-source CG (sm_cgbatch.cpp; one shard, always fp64): its own
-    // directions, Ad buffers, scalars and partials for bt_K columns, from the
+    // directions, Ad buffers, scalars and partials for bt.K columns, from the
     // first batched solve on and regrown for a larger K. Reads c->U at every
     // call; keeps nothing that depends on the gauge field.
-    int bt_K = 0;                   // columns the workspace holds
+    CGBatchWs bt;                   // the solver's workspace
     int bt_tiles = 0;               // test option batch_tiles=N: tiles per launch aimed at (0: kBatchTargetTiles)
-    double2 *bt_d[3] = {};          // d_i in bt_d[i mod 3], K x 2V complex each
-    double2 *bt_a[2] = {};          // Ad by pass parity
-    double2 *bt_partials = nullptr; // K x CGBatchCfg::pstride
-    sm::CGScalars *bt_sc = nullptr, *bt_h_sc = nullptr;  // K each: device, pinned host mirror
     // pion correlator: sources / solutions (bt_pion_K columns), source coordinates, C
     int bt_pion_K = 0;
     double2 *bt_phi = nullptr, *bt_x = nullptr;
@@ -347,6 +353,13 @@ int cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, 
 int cg_dev_mixed(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 void cg_mixed_free(sm_ctx *c);
 void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's workspaces (sm_cgbatch.cpp)
+// A batched solve's workspace for K columns on c's lattice (zeroed; SM_ERR_HIP
+// names the bytes on failure and leaves w empty), and the solve itself on any
+// such workspace: K columns of phi -> x, column b on l's links and mass.
+int cg_batch_ws_alloc(sm_ctx *c, CGBatchWs &w, int K);
+void cg_batch_ws_free(CGBatchWs &w);
+int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
+                   double tol, int max_iter, sm_cg_result *res);
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

@@ -38,15 +38,18 @@ __device__ __forceinline__ double2 ulink(const GArgs &a, int p, int x, int c) {
 // src/gauge_conf.cpp:45-49; sums as MeasureSp_HMC (:430-440) and
 // Compute_gaugeAction (:444-453): partial.x = sum Re U_01,
 // partial.y = sum beta Re(1 - U_01).
+__device__ __forceinline__ double2 plaquette_site(const GArgs &a, long n) {
+    const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
+    const int xp = x + 1 == a.Nx ? 0 : x + 1;
+    return cmul(cmul(cmul(a.U[n], ulink(a, 1, x, t + 1)), cconj(ulink(a, 0, xp, t))), cconj(a.U[n + a.V]));
+}
+
 __global__ void __launch_bounds__(256) plaquette_kernel(GArgs a, double beta, double2 *field,
                                                         double2 *partials) {
     __shared__ double2 sh[4];
     double2 acc = make_double2(0.0, 0.0);
     for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
-        const int xp = x + 1 == a.Nx ? 0 : x + 1;
-        const double2 P = cmul(cmul(cmul(a.U[n], ulink(a, 1, x, t + 1)), cconj(ulink(a, 0, xp, t))),
-                               cconj(a.U[n + a.V]));
+        const double2 P = plaquette_site(a, n);
         if (field) field[n] = P;
         acc.x += P.x;
         acc.y += beta * (1.0 - P.x);
@@ -60,25 +63,28 @@ __global__ void __launch_bounds__(256) plaquette_kernel(GArgs a, double beta, do
 //   S_1(n) = U_0(n) U_1(n+0) U*_0(n+1) + U*_0(n-0) U_1(n-0) U_0(n+1-0)
 //   F_mu(n) += -beta Im(U_mu(n) conj(S_mu(n)))
 // (0 = t direction, 1 = x direction; "n+1" is x+1, "n+0" is t+1.)
+__device__ __forceinline__ void staple_site(const GArgs &a, long n, double beta, double *F, double2 *staples) {
+    const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
+    const int xp = x + 1 == a.Nx ? 0 : x + 1, xm = x == 0 ? a.Nx - 1 : x - 1;
+    const double2 u0 = a.U[n], u1 = a.U[n + a.V];
+    const double2 S0 = cadd(cmul(cmul(u1, ulink(a, 0, xp, t)), cconj(ulink(a, 1, x, t + 1))),
+                            cmul(cmul(cconj(ulink(a, 1, xm, t)), ulink(a, 0, xm, t)), ulink(a, 1, xm, t + 1)));
+    const double2 S1 = cadd(cmul(cmul(u0, ulink(a, 1, x, t + 1)), cconj(ulink(a, 0, xp, t))),
+                            cmul(cmul(cconj(ulink(a, 0, x, t - 1)), ulink(a, 1, x, t - 1)), ulink(a, 0, xp, t - 1)));
+    if (staples) {
+        staples[n] = S0;
+        staples[n + a.V] = S1;
+    }
+    if (F) {
+        F[n] += -beta * cmul(u0, cconj(S0)).y;
+        F[n + a.V] += -beta * cmul(u1, cconj(S1)).y;
+    }
+}
+
 __global__ void __launch_bounds__(256) staple_force_kernel(GArgs a, double beta, double *F,
                                                            double2 *staples) {
-    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x) {
-        const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
-        const int xp = x + 1 == a.Nx ? 0 : x + 1, xm = x == 0 ? a.Nx - 1 : x - 1;
-        const double2 u0 = a.U[n], u1 = a.U[n + a.V];
-        const double2 S0 = cadd(cmul(cmul(u1, ulink(a, 0, xp, t)), cconj(ulink(a, 1, x, t + 1))),
-                                cmul(cmul(cconj(ulink(a, 1, xm, t)), ulink(a, 0, xm, t)), ulink(a, 1, xm, t + 1)));
-        const double2 S1 = cadd(cmul(cmul(u0, ulink(a, 1, x, t + 1)), cconj(ulink(a, 0, xp, t))),
-                                cmul(cmul(cconj(ulink(a, 0, x, t - 1)), ulink(a, 1, x, t - 1)), ulink(a, 0, xp, t - 1)));
-        if (staples) {
-            staples[n] = S0;
-            staples[n + a.V] = S1;
-        }
-        if (F) {
-            F[n] += -beta * cmul(u0, cconj(S0)).y;
-            F[n + a.V] += -beta * cmul(u1, cconj(S1)).y;
-        }
-    }
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x)
+        staple_site(a, n, beta, F, staples);
 }
 
 // ---- leapfrog link / momentum update (src/hmc.cpp:63-101) --------------------
@@ -86,24 +92,28 @@ __global__ void __launch_bounds__(256) staple_force_kernel(GArgs a, double beta,
 //   U *= exp(i coef P): std::exp of (+-0, coef*P) is glibc cexp = (cos y, sin y)
 //          for |y| > DBL_MIN and (1, y) below (s_cexp_template.c); then the
 //          plain complex product. coef = eps (full step) or 0.5*eps (half).
+__device__ __forceinline__ void md_update_link(long i, double2 *U, double *P, const double *F, double eps, int do_p,
+                                               double coef) {
+    double p = P[i];
+    if (do_p) {
+        p += eps * F[i];
+        P[i] = p;
+    }
+    const double y = coef * p;
+    double s, c;
+    if (fabs(y) > DBL_MIN) {
+        sincos(y, &s, &c);
+    } else {
+        s = y;
+        c = 1.0;
+    }
+    U[i] = cmul(U[i], make_double2(c, s));
+}
+
 __global__ void __launch_bounds__(256) md_update_kernel(long n2, double2 *U, double *P, const double *F,
                                                         double eps, int do_p, double coef) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x) {
-        double p = P[i];
-        if (do_p) {
-            p += eps * F[i];
-            P[i] = p;
-        }
-        const double y = coef * p;
-        double s, c;
-        if (fabs(y) > DBL_MIN) {
-            sincos(y, &s, &c);
-        } else {
-            s = y;
-            c = 1.0;
-        }
-        U[i] = cmul(U[i], make_double2(c, s));
-    }
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x)
+        md_update_link(i, U, P, F, eps, do_p, coef);
 }
 
 // ---- momentum kinetic energy: sum_n 0.5 P_0^2 + 0.5 P_1^2 (src/hmc.cpp:107-111)
@@ -133,30 +143,36 @@ __device__ __forceinline__ uint64_t global_site(const DrawArgs &a, long n, int &
 }
 
 // HMC::RandomPI (src/hmc.cpp:5-16): Pi_mu(n) ~ N(0, 1).
+__device__ __forceinline__ void draw_momenta_site(const DrawArgs &a, long n, double *P) {
+    int x, t;
+    const uint64_t ng = global_site(a, n, x, t);
+    double g1, g2;
+    sm_gauss2(a.seed, SM_STREAM_MOMENTA, ng, &g1, &g2);
+    P[n] = g1;
+    P[n + a.V] = g2;
+}
+
 __global__ void __launch_bounds__(256) draw_momenta_kernel(DrawArgs a, double *P) {
-    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x) {
-        int x, t;
-        const uint64_t ng = global_site(a, n, x, t);
-        double g1, g2;
-        sm_gauss2(a.seed, SM_STREAM_MOMENTA, ng, &g1, &g2);
-        P[n] = g1;
-        P[n + a.V] = g2;
-    }
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x)
+        draw_momenta_site(a, n, P);
 }
 
 // HMC::RandomCHI (src/hmc.cpp:19-28): Re, Im ~ N(0, 1/2) per spin component
 // (same streams and scaling as the host spinor generator).
-__global__ void __launch_bounds__(256) draw_source_kernel(DrawArgs a, double2 *chi) {
+__device__ __forceinline__ void draw_source_site(const DrawArgs &a, long n, double2 *chi) {
     const double s = 0.70710678118654752440084436210485;
-    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x) {
-        int x, t;
-        const uint64_t ng = global_site(a, n, x, t);
-        double g1, g2;
-        sm_gauss2(a.seed, 4, ng, &g1, &g2);
-        chi[n] = make_double2(s * g1, s * g2);
-        sm_gauss2(a.seed, 5, ng, &g1, &g2);
-        chi[n + a.V] = make_double2(s * g1, s * g2);
-    }
+    int x, t;
+    const uint64_t ng = global_site(a, n, x, t);
+    double g1, g2;
+    sm_gauss2(a.seed, 4, ng, &g1, &g2);
+    chi[n] = make_double2(s * g1, s * g2);
+    sm_gauss2(a.seed, 5, ng, &g1, &g2);
+    chi[n + a.V] = make_double2(s * g1, s * g2);
+}
+
+__global__ void __launch_bounds__(256) draw_source_kernel(DrawArgs a, double2 *chi) {
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x)
+        draw_source_site(a, n, chi);
 }
 
 // Gauge field of the host generator (sm_fields_fill_gauge), drawn in place.
@@ -170,6 +186,83 @@ __global__ void __launch_bounds__(256) draw_gauge_kernel(DrawArgs a, double sigm
             U[n + mu * a.V] = make_double2(re, im);
         }
     }
+}
+
+// ---- replica ensemble (sm_ens.cpp): R fields per launch, replica r = blockIdx.y
+// Replica r's fields lie r * 2V elements into each array, its parameters in
+// par[r] (block-uniform). Per replica every kernel runs the one-field kernel's
+// site function over the one-field kernel's grid along x, so the values, the
+// partials and their order are those of the one-field launch on that field.
+__global__ void __launch_bounds__(256) ens_draws_kernel(DrawArgs a, const EnsPar *par, double *P, double2 *chi) {
+    const long off = (long)blockIdx.y * 2 * a.V;
+    a.seed = par[blockIdx.y].seed;
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x) {
+        draw_momenta_site(a, n, P + off);
+        draw_source_site(a, n, chi + off);
+    }
+}
+
+__global__ void __launch_bounds__(256) ens_md_update_kernel(long n2, double2 *U, double *P, const double *F,
+                                                            const EnsPar *par, int do_p, double cfac) {
+    const long off = (long)blockIdx.y * n2;
+    const double eps = par[blockIdx.y].eps;
+    const double coef = cfac * eps;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x)
+        md_update_link(i, U + off, P + off, F + off, eps, do_p, coef);
+}
+
+__global__ void __launch_bounds__(256) ens_staple_force_kernel(GArgs a, const EnsPar *par, double *F) {
+    const long off = (long)blockIdx.y * 2 * a.V;
+    a.U += off;
+    const double beta = par[blockIdx.y].beta;
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x)
+        staple_site(a, n, beta, F + off, nullptr);
+}
+
+__global__ void __launch_bounds__(256) ens_plaquette_kernel(GArgs a, const EnsPar *par, double2 *partials) {
+    __shared__ double2 sh[4];
+    a.U += (long)blockIdx.y * 2 * a.V;
+    const double beta = par[blockIdx.y].beta;
+    double2 acc = make_double2(0.0, 0.0);
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < a.V; n += (long)gridDim.x * blockDim.x) {
+        const double2 P = plaquette_site(a, n);
+        acc.x += P.x;
+        acc.y += beta * (1.0 - P.x);
+    }
+    const double2 s = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[(long)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(256) ens_kinetic_kernel(long V, const double *P, double2 *partials) {
+    __shared__ double2 sh[4];
+    P += (long)blockIdx.y * 2 * V;
+    double2 acc = make_double2(0.0, 0.0);
+    for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < V; n += (long)gridDim.x * blockDim.x) {
+        acc.x += 0.5 * P[n] * P[n];
+        acc.x += 0.5 * P[n + V] * P[n + V];
+    }
+    const double2 s = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[(long)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// sum a conj(b) over a replica's 2V complex (include/variables.h:181-188's terms, this grid's order)
+__global__ void __launch_bounds__(256) ens_dot_kernel(long n2, const double2 *a, const double2 *b,
+                                                      double2 *partials) {
+    __shared__ double2 sh[4];
+    a += (long)blockIdx.y * n2;
+    b += (long)blockIdx.y * n2;
+    double2 acc = make_double2(0.0, 0.0);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (long)gridDim.x * blockDim.x)
+        acc = cadd(acc, cmul(a[i], cconj(b[i])));
+    const double2 s = block_sum(acc, sh);
+    if (threadIdx.x == 0) partials[(long)blockIdx.y * gridDim.x + blockIdx.x] = s;
+}
+
+// out[i] = row i's nparts partials in sum_partials_kernel's order (256 threads)
+__global__ void __launch_bounds__(256) ens_sums_kernel(int nparts, const double2 *partials, double2 *out) {
+    __shared__ double2 sh[4];
+    const double2 s = sum_partials_block(nparts, partials + (long)blockIdx.x * nparts, sh);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
 }
 
 // ---- launchers -----------------------------------------------------------------
@@ -234,6 +327,39 @@ void launch_draw_source(hipStream_t s, const Geometry &g, uint64_t seed, double2
 
 void launch_draw_gauge(hipStream_t s, const Geometry &g, uint64_t seed, double sigma, double2 *U) {
     hipLaunchKernelGGL(draw_gauge_kernel, dim3(grid_for(g.V)), dim3(256), 0, s, dargs(g, seed), sigma, U);
+}
+
+void launch_ens_draws(hipStream_t s, const Geometry &g, int R, const EnsPar *par, double *P, double2 *chi) {
+    hipLaunchKernelGGL(ens_draws_kernel, dim3(grid_for(g.V), R), dim3(256), 0, s, dargs(g, 0), par, P, chi);
+}
+
+void launch_ens_md_update(hipStream_t s, const Geometry &g, int R, double2 *U, double *P, const double *F,
+                          const EnsPar *par, int do_p, double cfac) {
+    hipLaunchKernelGGL(ens_md_update_kernel, dim3(grid_for(2 * g.V), R), dim3(256), 0, s, 2 * g.V, U, P, F, par, do_p,
+                       cfac);
+}
+
+void launch_ens_staple_force(hipStream_t s, const Geometry &g, int R, const double2 *U, const EnsPar *par, double *F) {
+    hipLaunchKernelGGL(ens_staple_force_kernel, dim3(grid_for(g.V), R), dim3(256), 0, s, gargs(g, 1, U, nullptr), par,
+                       F);
+}
+
+void launch_ens_plaquette(hipStream_t s, const Geometry &g, int R, const double2 *U, const EnsPar *par,
+                          double2 *partials) {
+    hipLaunchKernelGGL(ens_plaquette_kernel, dim3(gauge_reduce_blocks(g), R), dim3(256), 0, s,
+                       gargs(g, 1, U, nullptr), par, partials);
+}
+
+void launch_ens_kinetic(hipStream_t s, const Geometry &g, int R, const double *P, double2 *partials) {
+    hipLaunchKernelGGL(ens_kinetic_kernel, dim3(gauge_reduce_blocks(g), R), dim3(256), 0, s, g.V, P, partials);
+}
+
+void launch_ens_dot(hipStream_t s, const Geometry &g, int R, const double2 *a, const double2 *b, double2 *partials) {
+    hipLaunchKernelGGL(ens_dot_kernel, dim3(gauge_reduce_blocks(g), R), dim3(256), 0, s, 2 * g.V, a, b, partials);
+}
+
+void launch_ens_sums(hipStream_t s, const Geometry &g, int nrows, const double2 *partials, double2 *out) {
+    hipLaunchKernelGGL(ens_sums_kernel, dim3(nrows), dim3(256), 0, s, gauge_reduce_blocks(g), partials, out);
 }
 
 }  // namespace sm

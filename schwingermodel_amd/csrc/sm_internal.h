@@ -275,14 +275,28 @@ struct CGBatchCfg {
     long pstride;   // complex per column in the partials buffer
 };
 CGBatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles = 0);
+// The links and mass of each column: column b reads the field at U + b * ustride
+// (complex) and uses massv[b]. One field for all columns (sm_cg_batch, the
+// pion correlator): ustride = 0, massv = null and every column uses `mass`.
+// Both are block-uniform in every batched kernel (scalar registers).
+struct BatchLinks {
+    const double2 *U;
+    long ustride;
+    double mass;
+    const double *massv;  // device, K masses (m0 + 2), or null
+};
+inline BatchLinks shared_links(const double2 *U, double mass) { return BatchLinks{U, 0, mass, nullptr}; }
+// out_b = D in_b (dagger = 0) or D^dag in_b (1), one thread per site, K columns in one launch
+void launch_batch_apply(hipStream_t s, const Geometry &g, int K, int dagger, const double2 *in, double2 *out,
+                        const BatchLinks &l);
 // x = phi, T = D^dag phi, d0 = r_0 = phi - D T, and the columns' scalars (tol, max_iter, S_-1)
 void launch_cg_batch_init(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *phi, double2 *x,
-                          double2 *T, double2 *d0, const double2 *U, double mass, double tol, int max_iter,
-                          double2 *partials, CGScalars *sc);
+                          double2 *T, double2 *d0, const BatchLinks &l, double tol, int max_iter, double2 *partials,
+                          CGScalars *sc);
 // pass j of every column that is not done (and, without redundant scalars, its scalar step)
 void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *dold,
                           const double2 *rold, const double2 *aold, double2 *dnew, double2 *anew, double2 *x,
-                          const double2 *U, double mass, long pass, CGScalars *sc, double2 *partials);
+                          const BatchLinks &l, long pass, CGScalars *sc, double2 *partials);
 // redundant scalars: the last issued pass's state into sc for the host
 void launch_cg_batch_flush(hipStream_t s, const CGBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
                            long pass);
@@ -304,6 +318,32 @@ void launch_kinetic(hipStream_t s, const Geometry &g, const double *P, double2 *
 void launch_draw_momenta(hipStream_t s, const Geometry &g, uint64_t seed, double *P);
 void launch_draw_source(hipStream_t s, const Geometry &g, uint64_t seed, double2 *chi);
 void launch_draw_gauge(hipStream_t s, const Geometry &g, uint64_t seed, double sigma, double2 *U);
+
+// ---- replica ensemble (sm_ens.cpp): the MD kernels above for R fields in one launch ----
+// One shard. Replica r = blockIdx.y; its fields lie r * 2V elements into each
+// array (complex for U, chi and spinors, doubles for P and F). Every reduction
+// keeps the one-field kernel's grid (gauge_reduce_blocks(g) blocks of 256) per
+// replica and writes row r of `partials` (gauge_reduce_blocks(g) apart);
+// launch_ens_sums sums rows in launch_sum_partials' order, so a replica's sums
+// are bitwise those of the one-field path on the same field.
+struct EnsPar {
+    double beta;
+    double eps;      // tau / md_steps
+    uint64_t seed;   // sm_traj_seed(seed, traj)
+};
+void launch_ens_draws(hipStream_t s, const Geometry &g, int R, const EnsPar *par, double *P, double2 *chi);
+// do_p: P += eps_r F; then U *= exp(i (cfac eps_r) P), cfac = 0.5 or 1
+void launch_ens_md_update(hipStream_t s, const Geometry &g, int R, double2 *U, double *P, const double *F,
+                          const EnsPar *par, int do_p, double cfac);
+void launch_ens_staple_force(hipStream_t s, const Geometry &g, int R, const double2 *U, const EnsPar *par, double *F);
+void launch_ens_plaquette(hipStream_t s, const Geometry &g, int R, const double2 *U, const EnsPar *par,
+                          double2 *partials);
+void launch_ens_kinetic(hipStream_t s, const Geometry &g, int R, const double *P, double2 *partials);
+void launch_ens_dot(hipStream_t s, const Geometry &g, int R, const double2 *a, const double2 *b, double2 *partials);
+void launch_ens_sums(hipStream_t s, const Geometry &g, int nrows, const double2 *partials, double2 *out);
+// F_r = phi_dag_partialD_phi(U_r, l_r, r_r) (sm_kernels.hip, launch_force's arithmetic)
+void launch_ens_force(hipStream_t s, const Geometry &g, int R, const double2 *U, const double2 *l, const double2 *r,
+                      double *F);
 
 // ---- even-odd checkerboard (sm_eo.hip) ----
 void launch_to_cb(hipStream_t s, const Geometry &g, const double2 *full, double2 *e, double2 *o);

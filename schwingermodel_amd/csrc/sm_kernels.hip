@@ -357,7 +357,7 @@ struct FArgs {
     int Nx, Wt, t0, Ntg;
 };
 
-__global__ void __launch_bounds__(256) force_kernel(FArgs a) {
+__device__ __forceinline__ void force_sites(const FArgs &a) {
     const long V = a.V;
     for (long n = (long)blockIdx.x * blockDim.x + threadIdx.x; n < V; n += (long)gridDim.x * blockDim.x) {
         const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
@@ -387,6 +387,36 @@ __global__ void __launch_bounds__(256) force_kernel(FArgs a) {
                  cadd(cneg(R0), cmul(I_NUM, R1)));
         a.F[n + V] = cadd(P, Q).y;
     }
+}
+
+__global__ void __launch_bounds__(256) force_kernel(FArgs a) { force_sites(a); }
+
+// Replica ensemble (sm_ens.cpp): replica r = blockIdx.y, its fields r * 2V
+// elements into each array; one shard, so the t-faces are the field's own
+// columns (periodic wrap), as faces_for gives them to launch_force.
+__global__ void __launch_bounds__(256) ens_force_kernel(FArgs a) {
+    const long off = (long)blockIdx.y * 2 * a.V;
+    a.U += off;
+    a.l += off;
+    a.r += off;
+    a.F += off;
+    a.fl.hi = a.l;
+    a.fr.hi = a.r;
+    force_sites(a);
+}
+
+void launch_ens_force(hipStream_t s, const Geometry &g, int R, const double2 *U, const double2 *l, const double2 *r,
+                      double *F) {
+    FArgs a;
+    a.U = U; a.l = l; a.r = r; a.F = F;
+    a.fl = TFaces{};
+    a.fl.hi_xs = g.Wt;
+    a.fl.hi_ps = g.V;
+    a.fr = a.fl;
+    a.V = g.V; a.Nx = g.Nx; a.Wt = g.Wt; a.t0 = g.t0; a.Ntg = g.Ntg;
+    long nb = (g.V + 255) / 256;
+    if (nb > 4096) nb = 4096;
+    hipLaunchKernelGGL(ens_force_kernel, dim3((unsigned)nb, (unsigned)R), dim3(256), 0, s, a);
 }
 
 void launch_force(hipStream_t s, const Geometry &g, const double2 *U, const double2 *l,
