@@ -617,8 +617,8 @@ int sm_destroy(sm_ctx *c) {
         }
     stream_free(c, c->Uang);
     c->Uang = nullptr;
-    cg_mixed_free(c);
-    eo_cg_mixed_free(c);
+    mixed_free(c, c->mp);
+    mixed_free(c, c->eomp);
     cg_batch_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
@@ -1283,7 +1283,7 @@ int sm_cg_status(sm_ctx *c, sm_cg_result *res) {
 int sm_cg_dev(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter,
               sm_cg_result *res) {
     if (!res) return fail(SM_ERR_ARG, "null result");
-    if (c) c->mp_info = sm_cg_mixed_info{};
+    if (c) c->mp.info = sm_cg_mixed_info{};
     if (c && c->cg_precision == 1) return cg_dev_mixed(c, phi, x, m0, tol, max_iter, res);
     return cg_dev_fp64(c, phi, x, m0, tol, max_iter, res);
 }
@@ -1300,7 +1300,7 @@ int sm_cg_precision(sm_ctx *c, int mode, int *mode_out) {
 
 int sm_cg_mixed_last(const sm_ctx *c, sm_cg_mixed_info *out) {
     if (!c || !out) return fail(SM_ERR_ARG, "null argument");
-    *out = c->mp_info;
+    *out = c->mp.info;
     return SM_OK;
 }
 
@@ -1318,19 +1318,21 @@ int sm_host::cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, dou
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&c->sc->max_iter, max_iter, 1, c->stream));
         passes = max_iter + 1;
     }
-    CgChunker plan;
-    int issued = 0, chunk = plan.chunk;
-    while (issued < passes) {
-        const int nb = (passes - issued) < chunk ? (passes - issued) : chunk;
-        TRY(sm_cg_iterate(c, nb));
-        issued += nb;
-        TRY(sm_cg_status(c, res));
-        if (c->debug_cg)
-            fprintf(stderr, "[sm cg shard %d/%d] passes %d k %d err %.3e\n", c->shard, c->nshard, issued,
-                    res->iterations, res->residual);
-        if (res->converged) break;
-        chunk = plan.next(res->iterations, res->residual, tol * res->phi_norm);
-    }
+    int issued = 0;
+    TRY(cg_chunked(
+        passes,
+        [&](long nb) {
+            issued += (int)nb;
+            return sm_cg_iterate(c, (int)nb);
+        },
+        [&](CgStatus *st) {
+            TRY(sm_cg_status(c, res));
+            if (c->debug_cg)
+                fprintf(stderr, "[sm cg shard %d/%d] passes %d k %d err %.3e\n", c->shard, c->nshard, issued,
+                        res->iterations, res->residual);
+            *st = CgStatus{res->iterations, res->residual, tol * res->phi_norm, res->converged};
+            return SM_OK;
+        }));
     return sm_cg_finish(c, res);
 }
 

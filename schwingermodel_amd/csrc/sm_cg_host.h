@@ -1,0 +1,218 @@
+// sm_cg_host.h -- the control flow the CG hosts share, free of any device call
+// and of every HIP header so that tools/mixed_driver_check.cpp can run it
+// under the host sanitizers: the chunk planner and the chunked status loop of
+// every CG host but the batched one, and the reliable-update driver of the two
+// mixed-precision solvers (sm_cgmp.cpp, sm_eomp.cpp), which is described here
+// and nowhere else.
+#pragma once
+#include "../../include/sm_hip.h"
+
+#include <cmath>
+#include <cstdio>
+
+namespace sm {
+
+// Device-resident scalars of a mixed solve: a segment of fp32 inner iterations
+// between two fp64 true residuals (reliable updates). alpha and beta are real.
+struct MPScalars {
+    double alpha, beta;      // alpha_j, beta_j after pass j's scalar step (beta: the injection's before pass 0)
+    double alpha2, beta2;    // those of the pass before
+    double rn;               // iterated |r|^2 of the previous iteration
+    double err;              // iterated |r| of the last iteration
+    double M;                // largest iterated |r| since the segment began (starts at the true |r|)
+    double phi_norm, tol, delta;
+    double true_rr, phi_rr;  // |phi - D D^dag x|^2 (fp64) of the last update, |phi|^2
+    int k;                   // inner iterations of this segment
+    int k_total;             // inner iterations of the solve
+    int max_iter;            // bound on k_total
+    int done;                // the segment is over: every later pass and scalar step is a no-op
+    int bad;                 // it ended on a non-finite scalar (or <d,Ad> <= 0)
+    int pad;
+};
+
+}  // namespace sm
+
+namespace sm_host {
+
+int fail(int code, const char *fmt, ...);
+
+#define TRY(expr)                     \
+    do {                              \
+        int rc_ = (expr);             \
+        if (rc_ != SM_OK) return rc_; \
+    } while (0)
+
+// How many CG iterations to enqueue before the next status read. Kernels are
+// no-ops once the device's `done` flag is set, so queueing past convergence
+// costs empty launches and every status read costs a host round trip: predict
+// the iterations left to the stop test from the residual's observed geometric
+// rate, and stay a few percent past it.
+struct CgChunker {
+    int chunk = 4;
+    int k_prev = -1;
+    double err_prev = 0.0;
+    int next(int k, double err, double target) {
+        int c = chunk < 64 ? 2 * chunk : 64;
+        if (k_prev >= 0 && k > k_prev && err_prev > 0.0 && err > 0.0 && err < err_prev && target > 0.0) {
+            const double rate = std::pow(err / err_prev, 1.0 / (k - k_prev));
+            if (rate < 1.0) {
+                const double left = std::log(target / err) / std::log(rate);
+                c = left <= 0.0 ? 2 : (int)std::ceil(left * 1.05) + 1;
+                c = c < 2 ? 2 : (c > 256 ? 256 : c);
+            }
+        }
+        k_prev = k;
+        err_prev = err;
+        chunk = c;
+        return c;
+    }
+};
+
+// What a status read tells the planner: iterations done, the residual, what it
+// must reach, and whether the solve (or segment) is over.
+struct CgStatus {
+    int k;
+    double err, target;
+    int done;
+};
+
+// The chunked status loop of a CG host: up to `limit` passes, enqueued by
+// issue(nb) in chunks the planner sizes, each followed by the caller's own
+// read-back status(&st) -- whatever it launches, copies, waits for and prints
+// between a chunk's last pass and the read. Stops at st.done; *done (nullable)
+// says whether that was seen before the limit.
+template <class Issue, class Status>
+int cg_chunked(long limit, Issue issue, Status status, bool *done = nullptr) {
+    CgChunker plan;
+    int chunk = plan.chunk;
+    CgStatus st{};
+    for (long issued = 0; issued < limit && !st.done;) {
+        const long nb = (limit - issued) < chunk ? (limit - issued) : chunk;
+        TRY(issue(nb));
+        issued += nb;
+        TRY(status(&st));
+        if (!st.done) chunk = plan.next(st.k, st.err, st.target);
+    }
+    if (done) *done = st.done != 0;
+    return SM_OK;
+}
+
+// The reliable-update driver of the mixed-precision solvers, on operator A
+// (D D^dag or Dhat Dhat^dag) and vectors of the caller's kind:
+//
+//   x = phi; r = phi - A x in fp64; M = |r|
+//   segment: d_0 = fp32(r) + beta d_prev (first: beta = 0), y = 0, fp32 passes
+//       on y until the iterated |r| < delta M (M: the largest iterated |r| of
+//       the segment) or < tol |phi| -- decided on the device, read by the host
+//       in chunks (cg_chunked)
+//   reliable update: x += y (+ the pending alpha_{J-1} d_{J-1}), y = 0,
+//       r = phi - A x in fp64; stop if |r| < tol |phi|; else beta = |r|^2 /
+//       (the last iteration's iterated |r_{J-1}|^2) and the next segment
+//       starts from d_{J-1}: the search direction survives the replacement of
+//       the residual, so the updates cost almost no extra iterations (a
+//       restarted defect correction costs 20-50 % more on these operators).
+// The solve stops only on an fp64 true residual. Two consecutive updates that
+// fail to lower it, or a non-finite fp32 scalar, hand the rest to the fp64
+// solver: A e = r with its own x0 = r convention, x += e.
+//
+// Ops supplies every device call, and alone knows which solver it serves:
+//   h, info, d[3]            the scalars' host mirror, the solve's report, the direction buffers
+//   tol, max_iter, delta, force_fallback, debug, tag, stuck
+//   copy(a, b), add(x, e)    b = a, x += e in fp64
+//   true_residual(x, r, init, restart)   r = phi - A x, its scalars into h (init: the solve's first)
+//   inject(r, dprev, d0)     d0 = fp32(r) + beta dprev
+//   pass(j, d1, d2, dn)      pass j of the segment and its scalar step
+//   check(), read()          the launches' error state; that and the scalars into h
+//   fold(x, dlast, discard)  the reliable update's x += y, y = 0 (discard: y = 0 only)
+//   finish_vectors(&rhs, &e), solve64(rhs, e, tol, max_iter, &res)   the fp64 finish
+template <class Ops, class Vec>
+int cg_mixed_drive(Ops &o, const Vec *phi, Vec *x, Vec *r, sm_cg_result *res) {
+    const sm::MPScalars &h = o.h;
+    sm_cg_mixed_info &info = o.info;
+    const double tol = o.tol;
+    const int max_iter = o.max_iter;
+    info = sm_cg_mixed_info{};
+    info.used = 1;
+    if (x != phi) o.copy(phi, x);  // x = phi
+
+    int base = 0;  // d_i of the running segment lives in d[(base + i) mod 3], i >= -1
+    auto dbuf = [&](long i) { return o.d[(((base + i) % 3) + 3) % 3]; };
+    bool fallback = false;
+    int fails = 0;
+    double prev_true = 0.0;
+    TRY(o.true_residual(x, r, true, true));
+    for (;;) {
+        const double true_err = std::sqrt(h.true_rr);
+        if (o.debug)
+            fprintf(stderr, "[%s] update %d inner %d true %.3e (target %.3e)\n", o.tag, info.reliable_updates, h.k_total,
+                    true_err, tol * h.phi_norm);
+        if (info.reliable_updates > 0) fails = true_err < prev_true ? 0 : fails + 1;
+        prev_true = true_err;
+        if (!(true_err == true_err) || true_err < tol * h.phi_norm || h.k_total >= max_iter) break;
+        if (fails >= 2 || (o.force_fallback && info.reliable_updates >= 1)) {
+            fallback = true;
+            break;
+        }
+        // the segment: pass 0 on the injected direction, then passes 1, 2, ...
+        // until the device ends it; the state is read once per chunk
+        o.inject(r, dbuf(-1), dbuf(0));
+        long j = 0;
+        bool done;
+        TRY(cg_chunked(
+            (long)(max_iter - h.k_total) + 1,  // the device stops itself at max_iter
+            [&](long nb) {
+                for (long i = 0; i < nb; ++i, ++j)  // passes 0 and 1 both read d_0 and d_{-1}; pass 0 stores no d
+                    o.pass(j, j == 0 ? dbuf(0) : dbuf(j - 1), j == 0 ? dbuf(-1) : dbuf(j - 2), dbuf(j));
+                return SM_OK;
+            },
+            [&](CgStatus *st) {
+                TRY(o.read());
+                if (o.debug)
+                    fprintf(stderr, "[%s]   passes %ld k %d err %.3e M %.3e done %d\n", o.tag, j, h.k, h.err, h.M, h.done);
+                *st = CgStatus{h.k, h.err, std::fmax(o.delta * h.M, tol * h.phi_norm), h.done};
+                return SM_OK;
+            },
+            &done));
+        if (!done) return fail(SM_ERR_STATE, "%s", o.stuck);
+        info.inner_iterations = h.k_total;
+        const int J = h.k;
+        if (h.bad) {  // a non-finite scalar: y is not trusted, x and r are those of the last update
+            o.fold(x, dbuf(0), 1);
+            TRY(o.check());
+            fallback = true;
+            break;
+        }
+        o.fold(x, dbuf(J - 1), 0);
+        base = (int)((base + J) % 3);  // d_{J-1} becomes the next segment's d_{-1}, d_J's buffer takes its d_0
+        info.reliable_updates++;
+        TRY(o.true_residual(x, r, false, false));
+    }
+    info.inner_iterations = h.k_total;
+    double true_err = std::sqrt(h.true_rr);
+    const double phi_norm = h.phi_norm;
+    if (fallback && h.k_total < max_iter && true_err > 0.0) {
+        // the fp64 finish: A e = r (r kept apart: the fp64 solver's own buffers may include it)
+        Vec *rhs, *e;
+        TRY(o.finish_vectors(&rhs, &e));
+        o.copy(r, rhs);
+        sm_cg_result r64{};
+        TRY(o.solve64(rhs, e, tol * phi_norm / true_err, max_iter - h.k_total, &r64));
+        o.add(x, e);
+        info.fell_back = 1;
+        info.fp64_iterations = r64.iterations;
+        const int inner = h.k_total;
+        TRY(o.true_residual(x, r, false, true));
+        info.inner_iterations = inner;
+        true_err = std::sqrt(h.true_rr);
+    } else if (fallback) {
+        info.fell_back = 1;
+    }
+    info.true_residual = phi_norm > 0.0 ? true_err / phi_norm : true_err;
+    res->converged = true_err < tol * phi_norm ? 1 : 0;
+    res->iterations = info.inner_iterations + info.fp64_iterations;
+    res->residual = true_err;
+    res->phi_norm = phi_norm;
+    return SM_OK;
+}
+
+}  // namespace sm_host

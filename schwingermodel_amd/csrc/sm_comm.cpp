@@ -306,8 +306,8 @@ int halo4(sm_ctx *c, hipStream_t s, const double2 *field, double2 *recv) {
 
 int exchange_ghost_U(sm_ctx *c) {
     c->uang_state = 0;  // every change of U comes through here: the link codes are stale
-    c->mp_U_valid = false;  // and so are the fp32 links of the mixed-precision CG
-    c->eomp_U_valid = false;  // and those of the mixed-precision even-odd CG
+    c->mp.U_valid = false;  // and so are the fp32 links of the mixed-precision CG
+    c->eomp.U_valid = false;  // and those of the mixed-precision even-odd CG
     if (!c->sharded()) return SM_OK;
     // U_t(x, Wt-1) (plane 0 of my hi face) is the up-neighbour's U_t(x, -1)
     double2 *slo = face_buf(c, 1, 0), *shi = face_buf(c, 1, 1);

@@ -14,9 +14,7 @@
 #include "sm_internal.h"
 #include "sm_peer.h"
 
-namespace sm_host {
-
-int fail(int code, const char *fmt, ...);
+namespace sm_host {  // fail, TRY: sm_cg_host.h (through sm_internal.h)
 
 #define HIP_TRY(expr)                                                                   \
     do {                                                                                \
@@ -32,12 +30,6 @@ int fail(int code, const char *fmt, ...);
         if (r_ != ncclSuccess)                                                             \
             return ::sm_host::fail(SM_ERR_RCCL, "%s failed: %s (%s:%d)", #expr,             \
                                    ncclGetErrorString(r_), __FILE__, __LINE__);            \
-    } while (0)
-
-#define TRY(expr)                     \
-    do {                              \
-        int rc_ = (expr);             \
-        if (rc_ != SM_OK) return rc_; \
     } while (0)
 
 }  // namespace sm_host
@@ -56,6 +48,23 @@ struct CGBatchWs {
     double2 *a[2] = {};             // Ad by pass parity
     double2 *partials = nullptr;    // K x CGBatchCfg::pstride
     sm::CGScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
+};
+
+// State of a mixed-precision solver (sm_cgmp.cpp on the full lattice,
+// sm_eomp.cpp on one parity): its own directions, y, links, partials and
+// scalars, from the first mixed solve on; nothing shared with the fp64 paths.
+// n = the solver's vector length in complex entries (2V / V).
+struct MixedWs {
+    float2 *d[3] = {};              // the three direction buffers, n float2 each
+    float2 *a[2] = {};              // even-odd: Ad_j by pass parity
+    float2 *y = nullptr;            // the fp32 correction to x
+    float2 *U[2] = {};              // the links as the fp32 pass reads them (even-odd: even, odd)
+    bool U_valid = false;           // false after every change of U (exchange_ghost_U)
+    double2 *w = nullptr;           // even-odd: fp64 work r, Dhat^dag x, Dhat Dhat^dag x (3n)
+    double2 *fb = nullptr;          // fp64 finish: rhs and correction (2n; allocated on a fallback)
+    double2 *partials = nullptr;    // 2 per tile
+    sm::MPScalars *sc = nullptr, *h_sc = nullptr;  // device, pinned host mirror
+    sm_cg_mixed_info info{};        // the last solve
 };
 
 struct sm_ctx {
@@ -206,37 +215,18 @@ struct sm_ctx {
     long cg_issued = 0;             // iterations enqueued since sm_cg_begin
     int cg_pending_x = 0;           // fused path: last x update deferred to sm_cg_finish
     // mixed-precision CG (sm_cgmp.cpp; one shard): sm_cg_dev runs fp32 inner
-    // iterations with fp64 reliable updates when cg_precision == 1. Buffers
-    // from the first mixed solve on; its own scalars, partials and directions
-    // (nothing shared with the fp64 paths).
+    // iterations with fp64 reliable updates when cg_precision == 1.
     int cg_precision = 0;
     double mp_delta = 0.1;          // update when the iterated |r| < mp_delta * its maximum (test option mp_delta_pct)
     int mp_force_fallback = 0;      // test option: take the fp64 finish after the first update
-    float2 *mp_d[3] = {};           // the three direction buffers, 2V float2 each
-    float2 *mp_y = nullptr;         // the fp32 correction to x
-    float2 *mp_U = nullptr;         // the links as the fp32 pass reads them
-    bool mp_U_valid = false;        // false after every change of U (exchange_ghost_U)
-    double2 *mp_partials = nullptr; // 2 per tile
-    double2 *mp_fb = nullptr;       // fp64 finish: rhs and correction (4V complex; allocated on a fallback)
-    sm::MPScalars *mp_sc = nullptr, *mp_h_sc = nullptr;  // device, pinned host mirror
-    sm_cg_mixed_info mp_info{};     // the last sm_cg_dev
+    MixedWs mp;                     // info: the last sm_cg_dev
     // mixed-precision even-odd CG (sm_eomp.cpp; one shard): every even-odd
     // solve runs fp32 inner iterations (sm_eosp.hip) with fp64 reliable updates
     // when eo_cg_precision == 1. Independent of cg_precision; shares only the
-    // test options mp_delta / mp_force_fallback. Its buffers (from the first
-    // mixed even-odd solve on) are its own: neither eo / sc / partials / tick
-    // nor the mp_* state above is touched by the fp32 side.
+    // test options mp_delta / mp_force_fallback. Neither eo / sc / partials /
+    // tick nor the mp state above is touched by the fp32 side.
     int eo_cg_precision = 0;
-    float2 *eomp_d[3] = {};         // the three direction buffers, V float2 each (one parity)
-    float2 *eomp_a[2] = {};         // Ad_j by pass parity
-    float2 *eomp_y = nullptr;       // the fp32 correction to x
-    float2 *eomp_U[2] = {};         // even / odd links as the fp32 pass reads them
-    bool eomp_U_valid = false;      // false after every change of U (exchange_ghost_U)
-    double2 *eomp_w = nullptr;      // fp64 work: r, Dhat^dag x, Dhat Dhat^dag x (3V complex)
-    double2 *eomp_fb = nullptr;     // fp64 finish: rhs and correction (2V complex; allocated on a fallback)
-    double2 *eomp_partials = nullptr;
-    sm::MPScalars *eomp_sc = nullptr, *eomp_h_sc = nullptr;  // device, pinned host mirror
-    sm_cg_mixed_info eomp_info{};   // the last even-odd solve
+    MixedWs eomp;                   // info: the last even-odd solve
     // batched multi-source CG (sm_cgbatch.cpp; one shard, always fp64): its own
     // directions, Ad buffers, scalars and partials for bt.K columns, from the
     // first batched solve on and regrown for a larger K. Reads c->U at every
@@ -256,31 +246,7 @@ namespace sm_host {
 
 using namespace sm;
 
-// How many CG iterations to enqueue before the next status read. Kernels are
-// no-ops once the device's `done` flag is set, so queueing past convergence
-// costs empty launches and every status read costs a host round trip: predict
-// the iterations left to the stop test from the residual's observed geometric
-// rate, and stay a few percent past it.
-struct CgChunker {
-    int chunk = 4;
-    int k_prev = -1;
-    double err_prev = 0.0;
-    int next(int k, double err, double target) {
-        int c = chunk < 64 ? 2 * chunk : 64;
-        if (k_prev >= 0 && k > k_prev && err_prev > 0.0 && err > 0.0 && err < err_prev && target > 0.0) {
-            const double rate = std::pow(err / err_prev, 1.0 / (k - k_prev));
-            if (rate < 1.0) {
-                const double left = std::log(target / err) / std::log(rate);
-                c = left <= 0.0 ? 2 : (int)std::ceil(left * 1.05) + 1;
-                c = c < 2 ? 2 : (c > 256 ? 256 : c);
-            }
-        }
-        k_prev = k;
-        err_prev = err;
-        chunk = c;
-        return c;
-    }
-};
+// CgChunker and the chunked status loop of the CG hosts (cg_chunked): sm_cg_host.h
 
 // Largest face exchanged, in doubles per x: 4 columns x 2 planes x complex.
 constexpr size_t kMaxFaceDoubles = 16;
@@ -351,7 +317,48 @@ int placement_probe_default();            // candidates per buffer for new conte
 // to when the context's cg_precision is 1 (sm_cgmp.cpp)
 int cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 int cg_dev_mixed(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
-void cg_mixed_free(sm_ctx *c);
+void mixed_free(sm_ctx *c, MixedWs &w);  // either mixed solver's state
+// The device calls of cg_mixed_drive (sm_cg_host.h) that do not depend on the
+// operator. A solver adds true_residual, pass, fold and solve64 on its own.
+struct MixedDev {
+    sm_ctx *c;
+    MixedWs &w;
+    long n;                         // complex entries of a vector
+    const double2 *phi;
+    double tol;
+    int max_iter;
+    const char *tag, *stuck;        // of the debug lines; the error of a segment that does not end
+    const MPScalars &h = *w.h_sc;
+    sm_cg_mixed_info &info = w.info;
+    float2 *const *d = w.d;
+    double delta = c->mp_delta;
+    int force_fallback = c->mp_force_fallback, debug = c->debug_cg;
+    void copy(const double2 *a, double2 *b) { launch_copy(c->stream, n, a, b); }
+    void add(double2 *x, const double2 *e) { launch_mp_add(c->stream, n, x, e); }
+    void inject(const double2 *r, float2 *dprev, float2 *d0) { launch_mp_inject(c->stream, n, r, dprev, d0, w.sc); }
+    int check() {
+        HIP_TRY(hipGetLastError());
+        return SM_OK;
+    }
+    int read() {
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w.h_sc, w.sc, sizeof(MPScalars), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SM_OK;
+    }
+    // r = phi - Ax and what the driver decides on, read back
+    int residual(const double2 *Ax, double2 *r, bool init, bool restart) {
+        const int nb = launch_mp_residual(c->stream, n, phi, Ax, r, w.partials);
+        launch_mp_update(c->stream, nb, w.partials, w.sc, init ? 1 : 0, restart ? 1 : 0, tol, delta, max_iter);
+        return read();
+    }
+    int finish_vectors(double2 **rhs, double2 **e) {
+        if (!w.fb) HIP_TRY(hipMalloc(&w.fb, sizeof(double2) * 2 * (size_t)n));
+        *rhs = w.fb;
+        *e = w.fb + n;
+        return SM_OK;
+    }
+};
 void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's workspaces (sm_cgbatch.cpp)
 // A batched solve's workspace for K columns on c's lattice (zeroed; SM_ERR_HIP
 // names the bytes on failure and leaves w empty), and the solve itself on any
@@ -373,7 +380,6 @@ const double2 *eo_links(sm_ctx *c, int parity);  // the checkerboard links eo_re
 // every even-odd solve of the library: eo_cg, or eo_cg_mixed when eo_cg_precision == 1
 int eo_solve(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res);
 int eo_cg_mixed(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res);
-void eo_cg_mixed_free(sm_ctx *c);
 int eo_md_force(sm_ctx *c, const sm_hmc_params *p, const double2 *phi_full, double *F, sm_cg_result *res);
 int eo_fermion_action(sm_ctx *c, const sm_hmc_params *p, const double2 *phi_full, double *S, sm_cg_result *res);
 int eo_pseudofermion(sm_ctx *c, const sm_hmc_params *p, const double2 *chi_full, double2 *phi_full);

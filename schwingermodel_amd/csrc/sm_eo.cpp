@@ -154,6 +154,46 @@ static int eo_M(sm_ctx *c, const double2 *v, double2 *out, double mass, int *npa
     return eo_dhat(c, 0, W, out, mass, v, c->partials, nparts);
 }
 
+// The start of every fp64 CG on Dhat Dhat^dag: x = b, r_0 = b - M x, d_0 = r_0
+// (Ad: room for M x), and the solve's scalars from the init sums.
+static int eo_cg_start(sm_ctx *c, const double2 *b, double2 *x, double2 *Ad, double2 *r, double2 *d, double mass,
+                       double tol) {
+    const long n = c->g.V;  // complex entries of an even vector
+    const int nred = reduce_blocks(n);
+    if (x != b) launch_copy(c->stream, n, b, x);
+    int np;
+    TRY(eo_M(c, x, Ad, mass, &np));  // (its dot partials are not used)
+    double2 *prr = c->partials, *ppp = c->partials + nred;
+    launch_cg_init(c->stream, n, b, Ad, r, d, prr, ppp);
+    if (!c->sharded()) {
+        launch_cg_finalize_init(c->stream, nred, prr, ppp, c->sc, tol);
+    } else {
+        launch_sum_partials(c->stream, nred, prr, c->sums);
+        launch_sum_partials(c->stream, nred, ppp, c->sums + 1);
+        TRY(allreduce_dev(c, (double *)c->sums, 4));
+        launch_cg_init_from_sums(c->stream, c->sums, c->sc, tol);
+    }
+    return SM_OK;
+}
+
+// The status read of these solves (cg_chunked): the scalars to the host; all
+// ranks read the same, so every rank takes the same decisions.
+static int eo_cg_status(sm_ctx *c, double tol, CgStatus *st) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(c->h_sc, c->sc, sizeof(CGScalars), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *st = CgStatus{c->h_sc->k, c->h_sc->err, tol * c->h_sc->phi_norm, c->h_sc->done};
+    return SM_OK;
+}
+
+static int eo_cg_result(const sm_ctx *c, sm_cg_result *res) {
+    res->converged = c->h_sc->converged;
+    res->iterations = c->h_sc->k;
+    res->residual = c->h_sc->err;
+    res->phi_norm = c->h_sc->phi_norm;
+    return SM_OK;
+}
+
 // Folded CG on Dhat Dhat^dag (c->eo_cg_folded, needs the fused Dhat): the
 // one-pass recurrence of the full CG (cg_onepass_kernel / cg1_scalars) on
 // half-lattice vectors. Iteration j = pass A (r_j, d_j, x; W = Dhat^dag d_j)
@@ -163,23 +203,9 @@ static int eo_M(sm_ctx *c, const double2 *v, double2 *out, double mass, int *npa
 // BLAS-1 kernels: ~512 instead of 576 B per even site. r and d ping-pong.
 static int eo_cg_folded(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter,
                         sm_cg_result *res) {
-    const long n = c->g.V;
-    const int nred = reduce_blocks(n);
     double2 *Ad = eo_vec(c, EO_AD), *W = eo_vec(c, EO_W);
     double2 *rb[2] = {eo_vec(c, EO_R), eo_vec(c, EO_R2)}, *db[2] = {eo_vec(c, EO_D), eo_vec(c, EO_D2)};
-    if (x != b) launch_copy(c->stream, n, b, x);
-    int np;
-    TRY(eo_M(c, x, Ad, mass, &np));
-    double2 *prr = c->partials, *ppp = c->partials + nred;
-    launch_cg_init(c->stream, n, b, Ad, rb[0], db[0], prr, ppp);                // r_0 = b - M x_0; d_0 = r_0
-    if (!c->sharded()) {
-        launch_cg_finalize_init(c->stream, nred, prr, ppp, c->sc, tol);
-    } else {
-        launch_sum_partials(c->stream, nred, prr, c->sums);
-        launch_sum_partials(c->stream, nred, ppp, c->sums + 1);
-        TRY(allreduce_dev(c, (double *)c->sums, 4));
-        launch_cg_init_from_sums(c->stream, c->sums, c->sc, tol);
-    }
+    TRY(eo_cg_start(c, b, x, Ad, rb[0], db[0], mass, tol));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&c->sc->max_iter, max_iter, 1, c->stream));
     const EoFusedCfg cfg = eo_fused_config(c->g);
     const int nparts = eo_fused_blocks(cfg);
@@ -214,24 +240,15 @@ static int eo_cg_folded(sm_ctx *c, const double2 *b, double2 *x, double mass, do
         return SM_OK;
     };
     // pass 0 forms Ad_0; pass j >= 1 completes iteration j (the device stops
-    // itself at convergence or k = max_iter); all ranks read the same status
-    const long passes = (long)max_iter + 1;
-    CgChunker plan;
-    int chunk = plan.chunk;
-    while (j < passes) {
-        const long nb = (passes - j) < chunk ? (passes - j) : chunk;
-        for (long i = 0; i < nb; ++i) TRY(pass());
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->h_sc, c->sc, sizeof(CGScalars), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->h_sc->done) break;
-        chunk = plan.next(c->h_sc->k, c->h_sc->err, tol * c->h_sc->phi_norm);
-    }
-    res->converged = c->h_sc->converged;
-    res->iterations = c->h_sc->k;
-    res->residual = c->h_sc->err;
-    res->phi_norm = c->h_sc->phi_norm;
-    return SM_OK;
+    // itself at convergence or k = max_iter)
+    TRY(cg_chunked(
+        (long)max_iter + 1,
+        [&](long nb) {
+            for (long i = 0; i < nb; ++i) TRY(pass());
+            return SM_OK;
+        },
+        [&](CgStatus *st) { return eo_cg_status(c, tol, st); }));
+    return eo_cg_result(c, res);
 }
 
 // One-pass two-direction CG on Dhat Dhat^dag (c->eo_cg_td; t-shards of width
@@ -243,23 +260,10 @@ static int eo_cg_folded(sm_ctx *c, const double2 *b, double2 *x, double mass, do
 static int eo_cg_twodir(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter,
                         sm_cg_result *res) {
     const long n = c->g.V;
-    const int nred = reduce_blocks(n);
     double2 *dslot[3] = {eo_vec(c, EO_D2), eo_vec(c, EO_R), eo_vec(c, EO_D)};
     auto dbuf = [&](long i) { return dslot[((i % 3) + 3) % 3]; };
     double2 *abuf[2] = {eo_vec(c, EO_AD), eo_vec(c, EO_R2)};
-    if (x != b) launch_copy(c->stream, n, b, x);
-    int np;
-    TRY(eo_M(c, x, eo_vec(c, EO_AD), mass, &np));
-    double2 *prr = c->partials, *ppp = c->partials + nred;
-    launch_cg_init(c->stream, n, b, eo_vec(c, EO_AD), eo_vec(c, EO_R), eo_vec(c, EO_D), prr, ppp);  // r_0, d_0
-    if (!c->sharded()) {
-        launch_cg_finalize_init(c->stream, nred, prr, ppp, c->sc, tol);
-    } else {
-        launch_sum_partials(c->stream, nred, prr, c->sums);
-        launch_sum_partials(c->stream, nred, ppp, c->sums + 1);
-        TRY(allreduce_dev(c, (double *)c->sums, 4));
-        launch_cg_init_from_sums(c->stream, c->sums, c->sc, tol);
-    }
+    TRY(eo_cg_start(c, b, x, eo_vec(c, EO_AD), eo_vec(c, EO_R), eo_vec(c, EO_D), mass, tol));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)&c->sc->max_iter, max_iter, 1, c->stream));
     const EoTdCfg cfg = eo_td_config(c->g);
     const int nparts = eo_td_blocks(cfg);
@@ -302,31 +306,24 @@ static int eo_cg_twodir(sm_ctx *c, const double2 *b, double2 *x, double mass, do
         ++j;
         return SM_OK;
     };
-    const long passes = (long)max_iter + 1;
-    CgChunker plan;
-    int chunk = plan.chunk;
-    while (j < passes) {
-        const long nb = (passes - j) < chunk ? (passes - j) : chunk;
-        for (long i = 0; i < nb; ++i) TRY(pass());
-        if (red) launch_cg_ra_flush_sums(c->stream, c->sc, j - 1);  // the last pass's scalars for the host
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c->h_sc, c->sc, sizeof(CGScalars), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->debug_cg)
-            fprintf(stderr, "[sm eo_cg shard %d/%d] pass %ld k %d err %.3e target %.3e done %d\n", c->shard, c->nshard, j,
-                    c->h_sc->k, c->h_sc->err, tol * c->h_sc->phi_norm, c->h_sc->done);
-        if (c->h_sc->done) break;
-        chunk = plan.next(c->h_sc->k, c->h_sc->err, tol * c->h_sc->phi_norm);
-    }
+    CgStatus last;
+    TRY(cg_chunked(
+        (long)max_iter + 1,
+        [&](long nb) {
+            for (long i = 0; i < nb; ++i) TRY(pass());
+            if (red) launch_cg_ra_flush_sums(c->stream, c->sc, j - 1);  // the last pass's scalars for the host
+            return SM_OK;
+        },
+        [&](CgStatus *st) {
+            TRY(eo_cg_status(c, tol, st));
+            if (c->debug_cg)
+                fprintf(stderr, "[sm eo_cg shard %d/%d] pass %ld k %d err %.3e target %.3e done %d\n", c->shard, c->nshard,
+                        j, st->k, st->err, st->target, st->done);
+            return SM_OK;
+        }));
     launch_cg_td_finish_x(c->stream, n, x, dbuf(0), dbuf(1), dbuf(2), c->sc);  // odd final pass: pending alpha d
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_sc, c->sc, sizeof(CGScalars), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    res->converged = c->h_sc->converged;
-    res->iterations = c->h_sc->k;
-    res->residual = c->h_sc->err;
-    res->phi_norm = c->h_sc->phi_norm;
-    return SM_OK;
+    TRY(eo_cg_status(c, tol, &last));
+    return eo_cg_result(c, res);
 }
 
 // CG on Dhat Dhat^dag x = b (x0 = b, the reference's convention), the
@@ -337,43 +334,22 @@ int eo_cg(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int 
     const long n = c->g.V;  // complex entries of an even vector
     const int nparts = reduce_blocks(n);
     double2 *r = eo_vec(c, EO_R), *d = eo_vec(c, EO_D), *Ad = eo_vec(c, EO_AD);
-    if (x != b) launch_copy(c->stream, n, b, x);
-    int np;
-    TRY(eo_M(c, x, Ad, mass, &np));                          // (its dot partials are not used)
-    double2 *prr = c->partials, *ppp = c->partials + nparts;
-    launch_cg_init(c->stream, n, b, Ad, r, d, prr, ppp);
-    if (!c->sharded()) {
-        launch_cg_finalize_init(c->stream, nparts, prr, ppp, c->sc, tol);
-    } else {
-        launch_sum_partials(c->stream, nparts, prr, c->sums);
-        launch_sum_partials(c->stream, nparts, ppp, c->sums + 1);
-        TRY(allreduce_dev(c, (double *)c->sums, 4));
-        launch_cg_init_from_sums(c->stream, c->sums, c->sc, tol);
-    }
-    // every rank takes the same decisions: the status read back is global
-    CgChunker plan;
-    int issued = 0, chunk = plan.chunk;
-    while (issued < max_iter) {
-        const int nb = (max_iter - issued) < chunk ? (max_iter - issued) : chunk;
-        for (int i = 0; i < nb; ++i) {
-            TRY(eo_M(c, d, Ad, mass, &np));                          // Ad and partials of <d, Ad>
-            TRY(cg_scalar(c, np, 0));                                // alpha
-            launch_cg_update_xr(c->stream, n, x, r, d, Ad, c->sc, c->partials);
-            TRY(cg_scalar(c, nparts, 1));                            // stop test, beta
-            launch_cg_update_d(c->stream, n, d, r, c->sc);
-        }
-        HIP_TRY(hipGetLastError());
-        issued += nb;
-        HIP_TRY(hipMemcpyAsync(c->h_sc, c->sc, sizeof(CGScalars), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        if (c->h_sc->done) break;
-        chunk = plan.next(c->h_sc->k, c->h_sc->err, tol * c->h_sc->phi_norm);
-    }
-    res->converged = c->h_sc->converged;
-    res->iterations = c->h_sc->k;
-    res->residual = c->h_sc->err;
-    res->phi_norm = c->h_sc->phi_norm;
-    return SM_OK;
+    TRY(eo_cg_start(c, b, x, Ad, r, d, mass, tol));
+    TRY(cg_chunked(
+        max_iter,
+        [&](long nb) {
+            for (long i = 0; i < nb; ++i) {
+                int np;
+                TRY(eo_M(c, d, Ad, mass, &np));                          // Ad and partials of <d, Ad>
+                TRY(cg_scalar(c, np, 0));                                // alpha
+                launch_cg_update_xr(c->stream, n, x, r, d, Ad, c->sc, c->partials);
+                TRY(cg_scalar(c, nparts, 1));                            // stop test, beta
+                launch_cg_update_d(c->stream, n, d, r, c->sc);
+            }
+            return SM_OK;
+        },
+        [&](CgStatus *st) { return eo_cg_status(c, tol, st); }));
+    return eo_cg_result(c, res);
 }
 
 const double2 *eo_links(sm_ctx *c, int parity) { return ucb(c, parity); }
@@ -382,7 +358,7 @@ const double2 *eo_links(sm_ctx *c, int parity) { return ucb(c, parity); }
 // or fp32 inner iterations with fp64 reliable updates (sm_eomp.cpp) when the
 // context's eo_cg_precision is 1 (sm_eo_cg_precision).
 int eo_solve(sm_ctx *c, const double2 *b, double2 *x, double mass, double tol, int max_iter, sm_cg_result *res) {
-    c->eomp_info = sm_cg_mixed_info{};
+    c->eomp.info = sm_cg_mixed_info{};
     if (c->eo_cg_precision == 1) return eo_cg_mixed(c, b, x, mass, tol, max_iter, res);
     return eo_cg(c, b, x, mass, tol, max_iter, res);
 }
@@ -505,7 +481,7 @@ int sm_eo_cg_precision(sm_ctx *c, int mode, int *mode_out) {
 
 int sm_eo_cg_mixed_last(const sm_ctx *c, sm_cg_mixed_info *out) {
     if (!c || !out) return fail(SM_ERR_ARG, "null argument");
-    *out = c->eomp_info;
+    *out = c->eomp.info;
     return SM_OK;
 }
 

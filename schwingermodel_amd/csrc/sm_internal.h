@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "sm_cg_host.h"
+
 namespace sm {
 
 // Device field layout: the reference's SoA spinor, i.e.
@@ -216,23 +218,7 @@ void launch_stream(hipStream_t s, int two, long n, const double2 *a, const doubl
                    int blocks);
 
 // ---- mixed-precision CG (sm_cgsp.hip; driver sm_cgmp.cpp) ----
-// Device-resident scalars of a mixed solve: a segment of fp32 inner iterations
-// between two fp64 true residuals (reliable updates). alpha and beta are real.
-struct MPScalars {
-    double alpha, beta;      // alpha_j, beta_j after pass j's scalar step (beta: the injection's before pass 0)
-    double alpha2, beta2;    // those of the pass before
-    double rn;               // iterated |r|^2 of the previous iteration
-    double err;              // iterated |r| of the last iteration
-    double M;                // largest iterated |r| since the segment began (starts at the true |r|)
-    double phi_norm, tol, delta;
-    double true_rr, phi_rr;  // |phi - D D^dag x|^2 (fp64) of the last update, |phi|^2
-    int k;                   // inner iterations of this segment
-    int k_total;             // inner iterations of the solve
-    int max_iter;            // bound on k_total
-    int done;                // the segment is over: every later pass and scalar step is a no-op
-    int bad;                 // it ended on a non-finite scalar (or <d,Ad> <= 0)
-    int pad;
-};
+// MPScalars, the device-resident scalars of a mixed solve: sm_cg_host.h
 // The fp32 pass's tiles: the recompute-Ad pass's shape (ra) without its t-strips.
 CGFusedCfg cg_sp_config(const Geometry &g, const CGFusedCfg &ra);
 // Pass `pass` of a segment (0: the injected direction, no store): d_{j-1} in
