@@ -518,7 +518,8 @@ int sm_eo_cg_mixed_last(const sm_ctx *ctx, sm_cg_mixed_info *out);
  * SM_ERR_STATE before a gauge upload; SM_ERR_HIP when the workspace cannot be
  * allocated (sm_last_error() names the bytes asked for; the context stays
  * usable).
- * Always fp64: sm_cg_precision and sm_eo_cg_precision do not reach it.
+ * fp64 unless sm_cg_batch_precision (below) says otherwise: sm_cg_precision
+ * and sm_eo_cg_precision do not reach it.
  * Traffic per site and column: 224 B per iteration (read d_{j-1}, d_{j-2},
  * Ad_{j-1}: 96; write d_j, Ad_j: 64; x read + written every other pass: 32
  * mean; links 32, from cache after the first column). Workspace, allocated at
@@ -537,6 +538,44 @@ int sm_cg_batch_dev(sm_ctx *ctx, int K, const double *phi, double *x, double m0,
 /* The same with host pointers (K columns in the layout above). */
 int sm_cg_batch(sm_ctx *ctx, int K, const double *phi, double *x, double m0, double tol, int max_iter,
                 sm_cg_result *res /* K */);
+/* Precision of sm_cg_batch, sm_cg_batch_dev and the solve inside
+ * sm_pion_correlator, and of nothing else: 0 = fp64 (default; the code above,
+ * unchanged), 1 = mixed; < 0 keeps. SM_ERR_ARG (mode stays as it was) for mode 1
+ * on sharded, host-staged, loopback and peer contexts and for other values;
+ * *mode_out (nullable) = current. Independent of sm_cg_precision and
+ * sm_eo_cg_precision in both directions; the replica ensemble stays fp64.
+ * Mixed: the scheme of sm_cg_precision applied to every column. The iterations
+ * run the batch's stored-Ad pass on float2 fields (112 instead of 224 B per
+ * site and column), K columns per launch, on a correction y_b to x_b; whenever
+ * column b's iterated residual has fallen by 10x its segment ends (the column
+ * idles until the slowest column's has), x_b += y_b and r_b = phi_b -
+ * D D^dag x_b is recomputed in fp64 for all open columns at once, and the
+ * search direction is kept. A column stops only on such a true residual
+ * (res[b].residual, converged), so x_b passes the fp64 stop test but is NOT the
+ * reference's iterate sequence; iterations = fp32 + fp64 iterations, bounded by
+ * max_iter per column. A column whose two consecutive updates fail to lower the
+ * true residual, or with a non-finite fp32 scalar (an all-zero or a huge
+ * source), finishes in fp64 after the others: D D^dag e = r_b through the fp64
+ * batched solver with K = 1, x_b += e. As in fp64, a column's bits depend on
+ * that column, the gauge field and the arguments only.
+ * Memory: 96 B of fp32 and 96 B of fp64 work per site and column (the fp64
+ * workspace of 160 B is not allocated unless a column takes the fp64 finish,
+ * and then for one column), allocated at the first mixed batched solve and
+ * regrown for a larger K; the fp32 links (16 B per site) are converted from
+ * the current gauge field at the start of every solve, so nothing derived from
+ * it is kept here either.
+ * When to switch it on (whole solves to 1e-10 against the fp64 batch, DESIGN.md
+ * section 3.8 has every row): from 128^2 with K >= 8 (1.14-1.27x) and from
+ * 256^2 for every K (1.44-1.48x; 1024^2: 1.55-1.75x). Not at 64^2 (0.69-0.86x
+ * for K <= 16, 1.03x at K = 64: two launches per iteration where the fp64
+ * batch has one) nor at 128^2 with K = 1. At 1024^2 K sequential sm_cg_dev
+ * solves in mixed mode (sm_cg_precision) are as fast or faster. */
+int sm_cg_batch_precision(sm_ctx *ctx, int mode, int *mode_out);
+/* The K columns of the context's last sm_cg_batch(_dev) or sm_pion_correlator
+ * (K = 2 nsrc), as sm_cg_mixed_last: out[b].used = 1 if it ran mixed, else all
+ * zero. SM_ERR_ARG when K is not that solve's column count. */
+int sm_cg_batch_mixed_last(const sm_ctx *ctx, int K, sm_cg_mixed_info *out /* K */);
+
 /* Pion correlator from nsrc point sources on the current gauge field. For
  * source s and spin a in {0, 1}: phi = the unit vector at site (src_x[s],
  * src_t[s]) of plane a (built on the device), y_a = (D D^dag)^-1 phi in ONE

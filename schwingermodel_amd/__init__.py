@@ -158,12 +158,37 @@ class Lattice:
         check(lib.sm_eo_cg_mixed_last(self.ctx, ctypes.byref(info)))
         return info
 
+    def cg_batch_precision(self, mode=None):
+        """Set ("double" / "mixed", or 0 / 1) and return the precision of
+        cg_batch and of the solve inside pion_correlator
+        (sm_cg_batch_precision; None only reads). Independent of cg_precision
+        and eo_cg_precision; one-shard contexts only. Mixed: every column
+        passes the fp64 stop test but is not the reference's iterate sequence."""
+        m = -1 if mode is None else self.PRECISIONS.get(mode, mode)
+        if not isinstance(m, int):
+            raise ValueError(f"batched CG precision {mode!r}: 'double' or 'mixed'")
+        cur = ctypes.c_int()
+        check(lib.sm_cg_batch_precision(self.ctx, m, ctypes.byref(cur)))
+        return "mixed" if cur.value == 1 else "double"
+
+    @property
+    def last_cg_batch_mixed(self):
+        """[sm_cg_mixed_info] of the K columns of the last cg_batch or
+        pion_correlator of this object (used = 0: it ran fp64; [] before the
+        first). sm_cg_batch_mixed_last serves callers of the C entry points."""
+        K = getattr(self, "_batch_K", 0)
+        if K < 1:
+            return []
+        info = (CGMixedInfo * K)()
+        check(lib.sm_cg_batch_mixed_last(self.ctx, K, info))
+        return list(info)
+
     def cg_batch(self, phi, m0, tol=None, max_iter=None):
         """Solve D D^dagger x_b = phi_b for K right-hand sides on the context's
         current gauge field in one batched solve (sm_cg_batch; no implicit
         upload). phi: complex128 of shape (K, 2, V), column b = (plane mu0,
-        plane mu1). Returns (x, [CGResult] * K); always fp64, each column with
-        its own stop test and iteration count."""
+        plane mu1). Returns (x, [CGResult] * K), each column with its own stop
+        test and iteration count; fp64 unless cg_batch_precision("mixed")."""
         if not isinstance(phi, np.ndarray) or phi.dtype != np.complex128:
             raise TypeError("cg_batch: phi must be a complex128 numpy array")
         if phi.ndim != 3 or phi.shape[1:] != (2, self.V) or phi.shape[0] < 1:
@@ -174,6 +199,7 @@ class Lattice:
         res = (CGResult * K)()
         check(lib.sm_cg_batch(self.ctx, K, _vp(phi), _vp(x), float(m0), float(CG.tol if tol is None else tol),
                               int(CG.max_iter if max_iter is None else max_iter), res))
+        self._batch_K = K
         return x, list(res)
 
     def pion_correlator(self, m0, sources, tol=None, max_iter=None):
@@ -190,6 +216,7 @@ class Lattice:
         res = (CGResult * max(2 * n, 1))()
         check(lib.sm_pion_correlator(self.ctx, float(m0), float(CG.tol if tol is None else tol),
                                      int(CG.max_iter if max_iter is None else max_iter), n, sx, st, _vp(C), res))
+        self._batch_K = 2 * n
         return C, list(res)
 
     def ensemble(self, R):

@@ -260,15 +260,15 @@ int sm_comm_unique_id(void *id_out, int id_bytes) {
 //   probe_min_mib=N     smallest field (MiB) whose context runs the probe
 //   link_angles=0|1     recompute-Ad pass reads the links as one-double codes
 //   ra_xchunk=N         recompute-Ad pass: N rows per tile (with ra_xbal=1: ceil(Nx/N) balanced chunks)
-//   batch_tiles=N       batched CG (sm_cgbatch.cpp): tiles per launch the tile height aims at
+//   batch_tiles=N       batched CG (sm_cgbatch.cpp, sm_cgbatchmp.cpp): tiles per launch the tile height aims at
 //   kernel_events=0|1   t-shard CG pass: hand-offs between the streams on events
 //                       recorded by the launches themselves (1, the default) or markers
 //   bt=64|128|256       Dirac apply t-columns per block
 //   eo_fused=0, eo_cg_td=0, eo_cg_folded=1   even-odd operator / CG forms
 //   debug_cg=1          CG host loops print their status (stderr)
-//   mp_force_fallback=1 mixed-precision CG: take the fp64 finish after the first
-//                       reliable update
-//   mp_delta_pct=N      mixed-precision CG: reliable update when the iterated
+//   mp_force_fallback=1 mixed-precision CG (all three solvers): take the fp64 finish
+//                       after the first reliable update
+//   mp_delta_pct=N      mixed-precision CG (all three): reliable update when the iterated
 //                       residual is below N % of its maximum (default 10)
 // An unknown key or a malformed value fails the creation.
 static int apply_test_opts(sm_ctx *c) {
@@ -620,6 +620,7 @@ int sm_destroy(sm_ctx *c) {
     mixed_free(c, c->mp);
     mixed_free(c, c->eomp);
     cg_batch_free(c);
+    cg_batch_mixed_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};

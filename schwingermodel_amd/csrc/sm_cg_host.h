@@ -1,14 +1,16 @@
 // sm_cg_host.h -- the control flow the CG hosts share, free of any device call
-// and of every HIP header so that tools/mixed_driver_check.cpp can run it
-// under the host sanitizers: the chunk planner and the chunked status loop of
-// every CG host but the batched one, and the reliable-update driver of the two
-// mixed-precision solvers (sm_cgmp.cpp, sm_eomp.cpp), which is described here
-// and nowhere else.
+// and of every HIP header so that tools/mixed_driver_check.cpp and
+// tools/batch_mixed_driver_check.cpp can run it under the host sanitizers: the
+// chunk planner of every CG host, the chunked status loop of the one-column
+// ones, the reliable-update driver of the two one-column mixed-precision
+// solvers (sm_cgmp.cpp, sm_eomp.cpp), which is described here and nowhere
+// else, and its K-column form for the batched solver (sm_cgbatchmp.cpp).
 #pragma once
 #include "../../include/sm_hip.h"
 
 #include <cmath>
 #include <cstdio>
+#include <vector>
 
 namespace sm {
 
@@ -27,7 +29,7 @@ struct MPScalars {
     int max_iter;            // bound on k_total
     int done;                // the segment is over: every later pass and scalar step is a no-op
     int bad;                 // it ended on a non-finite scalar (or <d,Ad> <= 0)
-    int pad;
+    int k_last;              // k of the segment before this one (the batched injection finds d_prev in ring slot (k_last - 1) mod 3)
 };
 
 }  // namespace sm
@@ -212,6 +214,137 @@ int cg_mixed_drive(Ops &o, const Vec *phi, Vec *x, Vec *r, sm_cg_result *res) {
     res->iterations = info.inner_iterations + info.fp64_iterations;
     res->residual = true_err;
     res->phi_norm = phi_norm;
+    return SM_OK;
+}
+
+// The same scheme for the K <= 64 columns of a batched solve (sm_cgbatchmp.cpp),
+// in rounds: inject for the open columns, passes in chunks until every open
+// column's segment has ended (one CgChunker per column, the longest wish wins,
+// all K scalar blocks read once per chunk), fold, one batched true residual,
+// then cg_mixed_drive's decisions column by column. A column whose segment
+// ended early idles until the round is over; a column that has stopped, or is
+// marked for the fp64 finish, is closed: nothing of it is touched again before
+// the finishes, which run one column at a time after the rounds. Every column
+// therefore takes the decisions cg_mixed_drive would take on it alone.
+//
+// Columns are named by bit masks (bit b = column b). Ops:
+//   h(b), info(b)            column b's scalars (host mirror) and report
+//   tol, max_iter, delta, force_fallback, debug, tag, stuck
+//   start()                  x = phi, every column
+//   true_residual(m, init, restart)   r_b = phi_b - A x_b and its scalars for b in m, all K mirrors read back
+//   inject(m)                d_0 = fp32(r) + beta d_prev, into the ring's fixed slots
+//   pass(j, m)               pass j of the round and its scalar step
+//   check(), read()          the launches' error state; that and all K scalar blocks into the mirrors
+//   fold(m, discard)         x += y, y = 0 for b in m (b in discard: y = 0 only)
+//   finish(b, tol, iters, &res)   the fp64 finish of column b: A e = r_b, x_b += e
+typedef unsigned long long ColMask;
+
+template <class Ops>
+int cg_mixed_drive_batch(Ops &o, int K, sm_cg_result *res) {
+    struct Col {
+        int fails = 0;
+        double prev_true = 0.0;
+        bool fallback = false;
+    };
+    if (K < 1 || K > 64) return fail(SM_ERR_ARG, "%s: K = %d outside 1..64", o.tag, K);
+    const double tol = o.tol;
+    const int max_iter = o.max_iter;
+    std::vector<Col> col((size_t)K);
+    for (int b = 0; b < K; ++b) {
+        o.info(b) = sm_cg_mixed_info{};
+        o.info(b).used = 1;
+    }
+    auto bit = [](int b) { return (ColMask)1 << b; };
+    ColMask open = K == 64 ? ~(ColMask)0 : bit(K) - 1;
+    o.start();
+    TRY(o.true_residual(open, true, true));
+    for (;;) {
+        for (int b = 0; b < K; ++b) {  // the head of cg_mixed_drive's loop
+            if (!(open & bit(b))) continue;
+            const sm::MPScalars &h = o.h(b);
+            sm_cg_mixed_info &info = o.info(b);
+            Col &c = col[(size_t)b];
+            const double true_err = std::sqrt(h.true_rr);
+            if (o.debug)
+                fprintf(stderr, "[%s] column %d update %d inner %d true %.3e (target %.3e)\n", o.tag, b,
+                        info.reliable_updates, h.k_total, true_err, tol * h.phi_norm);
+            if (info.reliable_updates > 0) c.fails = true_err < c.prev_true ? 0 : c.fails + 1;
+            c.prev_true = true_err;
+            if (!(true_err == true_err) || true_err < tol * h.phi_norm || h.k_total >= max_iter) {
+                open &= ~bit(b);
+            } else if (c.fails >= 2 || (o.force_fallback && info.reliable_updates >= 1)) {
+                c.fallback = true;
+                open &= ~bit(b);
+            }
+        }
+        if (!open) break;
+        o.inject(open);
+        long limit = 0;  // every column stops itself at its own max_iter
+        for (int b = 0; b < K; ++b)
+            if ((open & bit(b)) && (long)(max_iter - o.h(b).k_total) + 1 > limit) limit = (long)(max_iter - o.h(b).k_total) + 1;
+        std::vector<CgChunker> plan((size_t)K);
+        long j = 0;
+        int chunk = plan[0].chunk;
+        bool ended = false;
+        while (j < limit && !ended) {
+            const long nb = limit - j < chunk ? limit - j : chunk;
+            for (long i = 0; i < nb; ++i, ++j) o.pass(j, open);
+            TRY(o.read());
+            ended = true;
+            int wish = 2, running = 0;
+            for (int b = 0; b < K; ++b) {
+                const sm::MPScalars &h = o.h(b);
+                if (!(open & bit(b)) || h.done) continue;
+                ended = false;
+                ++running;
+                const int w = plan[(size_t)b].next(h.k, h.err, std::fmax(o.delta * h.M, tol * h.phi_norm));
+                if (w > wish) wish = w;
+            }
+            if (o.debug) fprintf(stderr, "[%s]   passes %ld running %d next chunk %d\n", o.tag, j, running, wish);
+            chunk = wish;
+        }
+        if (!ended) return fail(SM_ERR_STATE, "%s", o.stuck);
+        ColMask bad = 0;
+        for (int b = 0; b < K; ++b) {
+            if (!(open & bit(b))) continue;
+            const sm::MPScalars &h = o.h(b);
+            o.info(b).inner_iterations = h.k_total;
+            if (h.bad) {  // y is not trusted, x and r are those of the last update
+                bad |= bit(b);
+                col[(size_t)b].fallback = true;
+            } else {
+                o.info(b).reliable_updates++;
+            }
+        }
+        o.fold(open, bad);
+        if (bad) TRY(o.check());
+        open &= ~bad;
+        if (open) TRY(o.true_residual(open, false, false));
+    }
+    for (int b = 0; b < K; ++b) {
+        const sm::MPScalars &h = o.h(b);
+        sm_cg_mixed_info &info = o.info(b);
+        info.inner_iterations = h.k_total;
+        double true_err = std::sqrt(h.true_rr);
+        const double phi_norm = h.phi_norm;
+        if (col[(size_t)b].fallback && h.k_total < max_iter && true_err > 0.0) {
+            sm_cg_result r64{};
+            const int inner = h.k_total;
+            TRY(o.finish(b, tol * phi_norm / true_err, max_iter - h.k_total, &r64));
+            info.fell_back = 1;
+            info.fp64_iterations = r64.iterations;
+            TRY(o.true_residual(bit(b), false, true));
+            info.inner_iterations = inner;
+            true_err = std::sqrt(h.true_rr);
+        } else if (col[(size_t)b].fallback) {
+            info.fell_back = 1;
+        }
+        info.true_residual = phi_norm > 0.0 ? true_err / phi_norm : true_err;
+        res[b].converged = true_err < tol * phi_norm ? 1 : 0;
+        res[b].iterations = info.inner_iterations + info.fp64_iterations;
+        res[b].residual = true_err;
+        res[b].phi_norm = phi_norm;
+    }
     return SM_OK;
 }
 

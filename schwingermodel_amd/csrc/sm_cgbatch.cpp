@@ -10,7 +10,9 @@
 //           wish wins) and all K states are read once per chunk
 //   finish  x_b += alpha_{k-1} d_{k-1} where column b's iteration count is odd
 //
-// One-shard contexts only, always fp64 (sm_cg_precision does not reach it).
+// One-shard contexts only. fp64 unless sm_cg_batch_precision switched the entry
+// points below to the mixed-precision solver (sm_cgbatchmp.cpp), which shares
+// nothing with this one; sm_cg_precision does not reach either.
 // Everything it writes is its own (bt_* of sm_ctx): the stepwise solver, the
 // one behind sm_cg_dev, the mixed and the even-odd solvers find their buffers
 // and scalars as they left them. The gauge field is read from c->U at every
@@ -185,6 +187,16 @@ int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, dou
     return SM_OK;
 }
 
+// Every batched solve of the entry points below: this file's fp64 solver on the
+// context's workspace, or the mixed-precision one (sm_cg_batch_precision).
+static int batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
+                       sm_cg_result *res) {
+    c->bt_info.assign((size_t)K, sm_cg_mixed_info{});
+    if (c->bt_precision == 1) return cg_batch_mixed(c, K, phi, x, m0, tol, max_iter, res);
+    TRY(batch_ready(c, K));
+    return cg_batch_solve(c, c->bt, K, phi, x, shared_links(c->U, m0 + 2), tol, max_iter, res);
+}
+
 }  // namespace sm_host
 
 using namespace sm_host;
@@ -200,9 +212,7 @@ int sm_cg_batch_dev(sm_ctx *c, int K, const double *phi, double *x, double m0, d
     if ((const double *)x == phi) return fail(SM_ERR_ARG, "batched CG: x must not alias phi");
     if (max_iter < 0) return fail(SM_ERR_ARG, "batched CG: max_iter < 0");
     TRY(check_ready(c));
-    TRY(batch_ready(c, K));
-    return cg_batch_solve(c, c->bt, K, (const double2 *)phi, (double2 *)x, shared_links(c->U, m0 + 2), tol, max_iter,
-                          res);
+    return batch_solve(c, K, (const double2 *)phi, (double2 *)x, m0, tol, max_iter, res);
 }
 
 int sm_cg_batch(sm_ctx *c, int K, const double *phi, double *x, double m0, double tol, int max_iter,
@@ -215,8 +225,7 @@ int sm_cg_batch(sm_ctx *c, int K, const double *phi, double *x, double m0, doubl
     TRY(staging_ready(c, K));
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
     HIP_TRY(hipMemcpyAsync(c->bt_phi, phi, fb, hipMemcpyHostToDevice, c->stream));
-    TRY(batch_ready(c, K));
-    TRY(cg_batch_solve(c, c->bt, K, c->bt_phi, c->bt_x, shared_links(c->U, m0 + 2), tol, max_iter, res));
+    TRY(batch_solve(c, K, c->bt_phi, c->bt_x, m0, tol, max_iter, res));
     HIP_TRY(hipMemcpyAsync(x, c->bt_x, fb, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return SM_OK;
@@ -250,10 +259,9 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
     HIP_TRY(hipGetLastError());
     std::vector<sm_cg_result> own((size_t)K);
     sm_cg_result *r = res ? res : own.data();
-    TRY(batch_ready(c, K));
-    TRY(cg_batch_solve(c, c->bt, K, c->bt_phi, c->bt_x, shared_links(c->U, m0 + 2), tol, max_iter, r));
-    // S_a = D^dag y_a (the existing apply) into the solver's first Ad buffer, free after the solve
-    double2 *S = c->bt.a[0];
+    TRY(batch_solve(c, K, c->bt_phi, c->bt_x, m0, tol, max_iter, r));
+    // S_a = D^dag y_a (the existing apply) into the solver's first Ad buffer (mixed: its D^dag x), free after the solve
+    double2 *S = c->bt_precision == 1 ? c->btmp.t : c->bt.a[0];
     const long n = 2 * c->g.V;
     for (int k = 0; k < K; ++k) TRY(apply(c, c->bt_x + k * n, S + k * n, m0 + 2, 1, nullptr, nullptr, nullptr));
     launch_pion_slices(c->stream, c->g, nsrc, S, c->bt_C);

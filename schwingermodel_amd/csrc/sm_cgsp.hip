@@ -301,8 +301,6 @@ __global__ void __launch_bounds__(256) cg_sp_kernel(SPArgs a) {
     }
 }
 
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN
-
 // The scalar step after pass j of a segment (first: j == 0): the stop tests on
 // the direct |r_j|^2, then alpha_j and beta_j (sm_device.h cg1_eval, real).
 __global__ void __launch_bounds__(256) cg_sp_scalar_kernel(int ntiles, const double2 *part, MPScalars *sc, int first) {
@@ -316,36 +314,7 @@ __global__ void __launch_bounds__(256) cg_sp_scalar_kernel(int ntiles, const dou
     __syncthreads();
     const double2 s1 = block_sum(a1, sh);
     if (threadIdx.x != 0 || sc->done) return;
-    const double dA = s0.x, rA = s0.y, rr = s1.x, AA = s1.y;
-    if (!first) {
-        const double err = sqrt(rr);
-        sc->err = err;
-        sc->k += 1;
-        sc->k_total += 1;
-        if (!finite_d(rr)) {
-            sc->bad = 1;
-            sc->done = 1;
-            return;
-        }
-        if (err > sc->M) sc->M = err;
-        if (err < sc->tol * sc->phi_norm || err < sc->delta * sc->M || sc->k_total >= sc->max_iter) {
-            sc->done = 1;  // alpha = alpha_{j-1} and rn = |r_{j-1}|^2 stay for the fold and the injection
-            return;
-        }
-    }
-    const double al = rr / dA;
-    const double est = rr - 2.0 * al * rA + al * al * AA;  // |r_{j+1}|^2
-    const double be = est / rr;
-    if (!finite_d(al) || !finite_d(be) || !(dA > 0.0)) {
-        sc->bad = 1;
-        sc->done = 1;
-        return;
-    }
-    sc->rn = rr;
-    sc->alpha2 = sc->alpha;
-    sc->beta2 = sc->beta;
-    sc->alpha = al;
-    sc->beta = be;
+    mp_scalar_step(sc, first, s0.x, s0.y, s1.x, s1.y);
 }
 
 // Links for the fp32 pass: plane 0 = -SignR U_t / 2 (SignR = -1 at t = Nt - 1),
@@ -383,24 +352,7 @@ __global__ void __launch_bounds__(256) mp_update_kernel(int nparts, const double
     __shared__ double2 sh[4];
     const double2 s = sum_partials_block(nparts, part, sh);
     if (threadIdx.x != 0) return;
-    if (init) {
-        sc->phi_rr = s.y;
-        sc->phi_norm = sqrt(s.y);
-        sc->tol = tol;
-        sc->delta = delta;
-        sc->max_iter = max_iter;
-        sc->k_total = 0;
-        sc->rn = 0.0;
-    }
-    const double err = sqrt(s.x);
-    sc->true_rr = s.x;
-    sc->beta = restart || !(sc->rn > 0.0) ? 0.0 : s.x / sc->rn;
-    sc->alpha = sc->alpha2 = sc->beta2 = 0.0;
-    sc->err = err;
-    sc->M = err;
-    sc->k = 0;
-    sc->bad = 0;
-    sc->done = err < sc->tol * sc->phi_norm || sc->k_total >= sc->max_iter || !finite_d(s.x) ? 1 : 0;
+    mp_update_step(sc, s, init, restart, tol, delta, max_iter);
 }
 
 // d_0 = r + beta d_prev in fp32 (beta from mp_update_kernel). beta == 0 (the

@@ -67,6 +67,21 @@ struct MixedWs {
     sm_cg_mixed_info info{};        // the last solve
 };
 
+// State of the mixed-precision batched solver (sm_cgbatchmp.cpp) for K columns:
+// its own fp32 directions, Ad, y and links, the fp64 work of the true residual,
+// partials and scalars; nothing shared with the fp64 batch but the K = 1
+// workspace of the rare fp64 finish (sm_ctx::bt, whatever it holds).
+struct CGBatchMixedWs {
+    int K = 0;                      // columns it holds
+    float2 *d[3] = {};              // the direction ring, K x 2V float2 each
+    float2 *a[2] = {};              // Ad by pass parity
+    float2 *y = nullptr;            // the fp32 corrections
+    float2 *U = nullptr;            // the links as the fp32 pass reads them, converted at every solve
+    double2 *r = nullptr, *t = nullptr, *ax = nullptr;  // fp64: r, D^dag x (the finish's e), D D^dag x; K x 2V each
+    double2 *partials = nullptr;
+    sm::MPScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
+};
+
 struct sm_ctx {
     int device = 0;
     int nshard = 1, shard = 0;
@@ -227,12 +242,19 @@ struct sm_ctx {
     // tick nor the mp state above is touched by the fp32 side.
     int eo_cg_precision = 0;
     MixedWs eomp;                   // info: the last even-odd solve
-    // batched multi-source CG (sm_cgbatch.cpp; one shard, always fp64): its own
-    // directions, Ad buffers, scalars and partials for bt.K columns, from the
-    // first batched solve on and regrown for a larger K. Reads c->U at every
-    // call; keeps nothing that depends on the gauge field.
+    // batched multi-source CG (sm_cgbatch.cpp; one shard): its own directions,
+    // Ad buffers, scalars and partials for bt.K columns, from the first batched
+    // solve on and regrown for a larger K. Reads c->U at every call; keeps
+    // nothing that depends on the gauge field.
     CGBatchWs bt;                   // the solver's workspace
     int bt_tiles = 0;               // test option batch_tiles=N: tiles per launch aimed at (0: kBatchTargetTiles)
+    // sm_cg_batch(_dev) and the correlator's solve run fp32 inner iterations with
+    // fp64 reliable updates when bt_precision == 1 (sm_cgbatchmp.cpp). Independent
+    // of cg_precision and eo_cg_precision; shares only the test options mp_delta
+    // / mp_force_fallback. The replica ensemble does not look at it.
+    int bt_precision = 0;
+    CGBatchMixedWs btmp;
+    std::vector<sm_cg_mixed_info> bt_info;  // the columns of the last batched solve (all zero: it ran fp64)
     // pion correlator: sources / solutions (bt_pion_K columns), source coordinates, C
     int bt_pion_K = 0;
     double2 *bt_phi = nullptr, *bt_x = nullptr;
@@ -367,6 +389,11 @@ int cg_batch_ws_alloc(sm_ctx *c, CGBatchWs &w, int K);
 void cg_batch_ws_free(CGBatchWs &w);
 int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res);
+// The mixed-precision batched solve on the context's gauge field (sm_cgbatchmp.cpp):
+// K columns of phi -> x on the device, c->bt_info[b] = column b's report.
+int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
+                   sm_cg_result *res);
+void cg_batch_mixed_free(sm_ctx *c);
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

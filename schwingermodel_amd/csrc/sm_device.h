@@ -300,6 +300,71 @@ static __device__ __attribute__((noinline)) void ra_scalars_from_sums(CGScalars 
     *stop = s.done;
 }
 
+// ---- mixed-precision CG scalars (sm_cgsp.hip, sm_eosp.hip, sm_cgbatchsp.hip) ----
+__device__ __forceinline__ bool finite_d(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN
+
+// The scalar step after pass j of a segment (first: j == 0), by one thread, on
+// a segment that has not ended: the stop tests on the direct |r_j|^2, then
+// alpha_j and beta_j (cg1_eval, real).
+__device__ __forceinline__ void mp_scalar_step(MPScalars *sc, int first, double dA, double rA, double rr, double AA) {
+    if (!first) {
+        const double err = sqrt(rr);
+        sc->err = err;
+        sc->k += 1;
+        sc->k_total += 1;
+        if (!finite_d(rr)) {
+            sc->bad = 1;
+            sc->done = 1;
+            return;
+        }
+        if (err > sc->M) sc->M = err;
+        if (err < sc->tol * sc->phi_norm || err < sc->delta * sc->M || sc->k_total >= sc->max_iter) {
+            sc->done = 1;  // alpha = alpha_{j-1} and rn = |r_{j-1}|^2 stay for the fold and the injection
+            return;
+        }
+    }
+    const double al = rr / dA;
+    const double est = rr - 2.0 * al * rA + al * al * AA;  // |r_{j+1}|^2
+    const double be = est / rr;
+    if (!finite_d(al) || !finite_d(be) || !(dA > 0.0)) {
+        sc->bad = 1;
+        sc->done = 1;
+        return;
+    }
+    sc->rn = rr;
+    sc->alpha2 = sc->alpha;
+    sc->beta2 = sc->beta;
+    sc->alpha = al;
+    sc->beta = be;
+}
+
+// The true residual's norm s = (|r|^2, |phi|^2) into sc and the next segment's
+// start: M = |r|, beta = |r|^2 / (the previous iterated |r|^2) for the
+// injection (restart: 0), done = 1 when the true residual passes the stop test
+// or no iteration is left. k_last keeps the ended segment's iteration count.
+__device__ __forceinline__ void mp_update_step(MPScalars *sc, double2 s, int init, int restart, double tol,
+                                               double delta, int max_iter) {
+    if (init) {
+        sc->phi_rr = s.y;
+        sc->phi_norm = sqrt(s.y);
+        sc->tol = tol;
+        sc->delta = delta;
+        sc->max_iter = max_iter;
+        sc->k_total = 0;
+        sc->rn = 0.0;
+    }
+    const double err = sqrt(s.x);
+    sc->true_rr = s.x;
+    sc->beta = restart || !(sc->rn > 0.0) ? 0.0 : s.x / sc->rn;
+    sc->alpha = sc->alpha2 = sc->beta2 = 0.0;
+    sc->err = err;
+    sc->M = err;
+    sc->k_last = init ? 0 : sc->k;
+    sc->k = 0;
+    sc->bad = 0;
+    sc->done = err < sc->tol * sc->phi_norm || sc->k_total >= sc->max_iter || !finite_d(s.x) ? 1 : 0;
+}
+
 // A block-uniform double2 (e.g. read back from LDS) into scalar registers.
 __device__ __forceinline__ double2 uniform_d2(double2 v) {
     return make_double2(__hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v.x)),

@@ -288,6 +288,28 @@ void launch_cg_batch_flush(hipStream_t s, const CGBatchCfg &c, int K, const doub
                            long pass);
 void launch_cg_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
                               const double2 *d1, const double2 *d2, const CGScalars *sc);
+// ---- mixed-precision batched CG (sm_cgbatchsp.hip; driver sm_cgbatchmp.cpp) ----
+// Every launch serves the columns of `mask` (bit b = column b, K <= 64) and
+// leaves the others alone. The direction ring d[3] holds d_i of the running
+// round in d[i mod 3] for every column (d_{-1} in d[2]); ad[2]: Ad by pass parity.
+static_assert(kBatchMax <= 64, "the batched mixed-precision kernels name their columns in a 64-bit mask");
+// Pass `pass` of a round (0: the injected direction, no d store; even passes
+// >= 2 update y) and its scalar step, c's tiles; partials: K x 2 c.P complex.
+void launch_cg_batch_sp(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, unsigned long long mask,
+                        float2 *const d[3], float2 *const ad[2], float2 *y, const float2 *U32, double mass, long pass,
+                        MPScalars *sc, double2 *partials);
+int batch_mp_blocks(const Geometry &g);  // blocks per column of the three kernels below (the lattice's alone)
+// r_b = phi_b - Ax_b and launch_mp_update's step on column b's scalars; partials: K x batch_mp_blocks(g)
+void launch_batch_mp_residual(hipStream_t s, const Geometry &g, int K, unsigned long long mask, const double2 *phi,
+                              const double2 *Ax, double2 *r, double2 *partials, MPScalars *sc, int init, int restart,
+                              double tol, double delta, int max_iter);
+// d[0] = fp32(r) + beta_b d_prev, d[2] = d_prev = the ended segment's last direction, wherever the ring holds it
+void launch_batch_mp_inject(hipStream_t s, const Geometry &g, int K, unsigned long long mask, const double2 *r,
+                            float2 *const d[3], const MPScalars *sc);
+// x_b += y_b plus the pending alpha_{J-1} d_{J-1} after an odd J_b, y_b = 0; columns of `discard`: y_b = 0 only
+void launch_batch_mp_fold(hipStream_t s, const Geometry &g, int K, unsigned long long mask, unsigned long long discard,
+                          double2 *x, float2 *y, float2 *const d[3], const MPScalars *sc);
+
 void launch_point_sources(hipStream_t s, const Geometry &g, int K, const int *sx, const int *st, double2 *phi);
 void launch_pion_slices(hipStream_t s, const Geometry &g, int nsrc, const double2 *S, double *C);
 

@@ -2,7 +2,7 @@
 """Batched multi-source CG against K sequential sm_cg_dev solves, whole solves to 1e-10.
 
     python tools/batch_cg_bench.py [--sizes 64,128,256,1024] [--ks 1,2,4,8,16,32,64] [--pairs 3]
-                                   [--tiles N] [--out FILE]
+                                   [--tiles N] [--precision double|mixed|both] [--out FILE]
 
 Per size (sigma 0.2374, m0 -0.06: configs 2 and 3 of BASELINE.md): one context,
 K sources from K distinct sm_fill_spinor seeds. Per K, after one warm-up of
@@ -18,6 +18,15 @@ the medians, sequential over batch. --tiles N sets the test option
 batch_tiles (tiles per launch the batch's tile height aims at; tuning runs).
 The records go to stdout as JSON lines and, together, to
 profiles/cg_batch_<build id>.json (or --out).
+
+--precision mixed runs both sides in mixed precision (sm_cg_batch_precision and
+sm_cg_precision = 1). --precision both compares the batch with itself: the
+sides are the fp64 batch and the mixed batch of the same build and context
+(sm_cg_batch_precision switched between the solves), from --seq-from sites per
+side (default 1024) also K sequential mixed sm_cg_dev solves, which is what a
+caller there has today. Its records carry time_ratio_fp64_over_mixed, the fp64
+side's spread and `credited` (mixed beats fp64 by more than that spread), and
+go to profiles/cg_batch_mixed_<build id>.json.
 """
 import argparse
 import ctypes
@@ -41,6 +50,8 @@ def main():
     ap.add_argument("--tol", type=float, default=1e-10)
     ap.add_argument("--max-iter", type=int, default=100000)
     ap.add_argument("--tiles", type=int, default=0, help="test option batch_tiles (0: the library's default)")
+    ap.add_argument("--precision", choices=("double", "mixed", "both"), default="double")
+    ap.add_argument("--seq-from", type=int, default=1024, help="--precision both: sequential mixed sm_cg_dev side from this N")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.tiles:
@@ -68,9 +79,15 @@ def main():
         sm.check(sm.lib.sm_upload_gauge_dev(L.ctx, vp(dU.data_ptr())))
         sm.check(sm.lib.sm_synchronize(L.ctx))
         stride = 4 * V * 8
+        if a.precision == "mixed":
+            sm.check(sm.lib.sm_cg_batch_precision(L.ctx, 1, None))
+        if a.precision != "double":
+            sm.check(sm.lib.sm_cg_precision(L.ctx, 1, None))
 
-        def batch(K):
+        def batch(K, mode=None):
             res = (sm.CGResult * K)()
+            if mode is not None:
+                sm.check(sm.lib.sm_cg_batch_precision(L.ctx, mode, None))
             torch.cuda.synchronize()
             t = time.perf_counter()
             sm.check(sm.lib.sm_cg_batch_dev(L.ctx, K, vp(dphi.data_ptr()), vp(xb.data_ptr()), a.m0, a.tol, a.max_iter, res))
@@ -92,13 +109,18 @@ def main():
 
         for K in ks:
             sides = {"batch": batch, "sequential": sequential}
+            if a.precision == "both":
+                sides = {"batch_fp64": lambda K: batch(K, 0), "batch_mixed": lambda K: batch(K, 1)}
+                if N >= a.seq_from:
+                    sides["sequential_mixed"] = sequential
             out = {name: [] for name in sides}
             for fn in sides.values():
                 fn(K)  # warm-up (the first batched solve of a larger K also regrows the workspace)
             for _ in range(a.pairs):
                 for name, fn in sides.items():
                     out[name].append(fn(K))
-            rec = {"N": N, "K": K, "build_id": build_id, "tol": a.tol, "pairs": a.pairs, "tiles": a.tiles}
+            rec = {"N": N, "K": K, "build_id": build_id, "tol": a.tol, "pairs": a.pairs, "tiles": a.tiles,
+                   "precision": a.precision}
             for name, runs in out.items():
                 walls = [r[0] for r in runs]
                 med = statistics.median(walls)
@@ -108,14 +130,23 @@ def main():
                              "us_per_iteration": round(med * 1e6 / max(max(its), 1), 3),
                              "us_per_iteration_per_column": round(med * 1e6 / max(sum(its), 1), 3),
                              "spread": round((max(walls) - min(walls)) / med, 4)}
-            rec["time_ratio_sequential_over_batch"] = round(rec["sequential"]["median_ms"] / rec["batch"]["median_ms"], 3)
-            rec["x_max_rel_diff"] = float(((xb[:K] - xs[:K]).norm(dim=1) / xs[:K].norm(dim=1)).max())
+            if a.precision == "both":
+                ratio = rec["batch_fp64"]["median_ms"] / rec["batch_mixed"]["median_ms"]
+                rec["time_ratio_fp64_over_mixed"] = round(ratio, 3)
+                rec["credited"] = bool(ratio > 1.0 + rec["batch_fp64"]["spread"])
+                if "sequential_mixed" in rec:
+                    rec["time_ratio_sequential_mixed_over_batch_mixed"] = round(
+                        rec["sequential_mixed"]["median_ms"] / rec["batch_mixed"]["median_ms"], 3)
+            else:
+                rec["time_ratio_sequential_over_batch"] = round(rec["sequential"]["median_ms"] / rec["batch"]["median_ms"], 3)
+                rec["x_max_rel_diff"] = float(((xb[:K] - xs[:K]).norm(dim=1) / xs[:K].norm(dim=1)).max())
             print(json.dumps(rec), flush=True)
             records.append(rec)
         L.close()
         del dphi, xb, xs, dU
         torch.cuda.empty_cache()
-    path = a.out or os.path.join(REPO, "profiles", f"cg_batch_{build_id}.json")
+    stem = "cg_batch_mixed" if a.precision == "both" else "cg_batch"
+    path = a.out or os.path.join(REPO, "profiles", f"{stem}_{build_id}.json")
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         json.dump({"build_id": build_id, "records": records}, f, indent=1)
