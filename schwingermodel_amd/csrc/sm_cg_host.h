@@ -1,10 +1,11 @@
 // sm_cg_host.h -- the control flow the CG hosts share, free of any device call
 // and of every HIP header so that tools/mixed_driver_check.cpp and
 // tools/batch_mixed_driver_check.cpp can run it under the host sanitizers: the
-// chunk planner of every CG host, the chunked status loop of the one-column
-// ones, the reliable-update driver of the two one-column mixed-precision
-// solvers (sm_cgmp.cpp, sm_eomp.cpp), which is described here and nowhere
-// else, and its K-column form for the batched solver (sm_cgbatchmp.cpp).
+// chunk planner of every CG host, the chunked status loop of the fp64
+// one-column ones, and the reliable-update driver of the three mixed-precision
+// solvers (sm_cgmp.cpp, sm_eomp.cpp, sm_cgbatchmp.cpp), which is described
+// here and nowhere else: one loop on K columns, and MixedColumn, which hands it
+// a one-column solver's operations as K = 1.
 #pragma once
 #include "../../include/sm_hip.h"
 
@@ -100,139 +101,41 @@ int cg_chunked(long limit, Issue issue, Status status, bool *done = nullptr) {
 }
 
 // The reliable-update driver of the mixed-precision solvers, on operator A
-// (D D^dag or Dhat Dhat^dag) and vectors of the caller's kind:
+// (D D^dag or Dhat Dhat^dag) and K <= 64 columns, each a solve of its own:
 //
 //   x = phi; r = phi - A x in fp64; M = |r|
 //   segment: d_0 = fp32(r) + beta d_prev (first: beta = 0), y = 0, fp32 passes
 //       on y until the iterated |r| < delta M (M: the largest iterated |r| of
 //       the segment) or < tol |phi| -- decided on the device, read by the host
-//       in chunks (cg_chunked)
+//       in chunks
 //   reliable update: x += y (+ the pending alpha_{J-1} d_{J-1}), y = 0,
 //       r = phi - A x in fp64; stop if |r| < tol |phi|; else beta = |r|^2 /
 //       (the last iteration's iterated |r_{J-1}|^2) and the next segment
 //       starts from d_{J-1}: the search direction survives the replacement of
 //       the residual, so the updates cost almost no extra iterations (a
 //       restarted defect correction costs 20-50 % more on these operators).
-// The solve stops only on an fp64 true residual. Two consecutive updates that
-// fail to lower it, or a non-finite fp32 scalar, hand the rest to the fp64
-// solver: A e = r with its own x0 = r convention, x += e.
+// A column stops only on an fp64 true residual. Two consecutive updates that
+// fail to lower it, or a non-finite fp32 scalar, hand the rest of that column
+// to the fp64 solver: A e = r with its own x0 = r convention, x += e.
 //
-// Ops supplies every device call, and alone knows which solver it serves:
-//   h, info, d[3]            the scalars' host mirror, the solve's report, the direction buffers
-//   tol, max_iter, delta, force_fallback, debug, tag, stuck
-//   copy(a, b), add(x, e)    b = a, x += e in fp64
-//   true_residual(x, r, init, restart)   r = phi - A x, its scalars into h (init: the solve's first)
-//   inject(r, dprev, d0)     d0 = fp32(r) + beta dprev
-//   pass(j, d1, d2, dn)      pass j of the segment and its scalar step
-//   check(), read()          the launches' error state; that and the scalars into h
-//   fold(x, dlast, discard)  the reliable update's x += y, y = 0 (discard: y = 0 only)
-//   finish_vectors(&rhs, &e), solve64(rhs, e, tol, max_iter, &res)   the fp64 finish
-template <class Ops, class Vec>
-int cg_mixed_drive(Ops &o, const Vec *phi, Vec *x, Vec *r, sm_cg_result *res) {
-    const sm::MPScalars &h = o.h;
-    sm_cg_mixed_info &info = o.info;
-    const double tol = o.tol;
-    const int max_iter = o.max_iter;
-    info = sm_cg_mixed_info{};
-    info.used = 1;
-    if (x != phi) o.copy(phi, x);  // x = phi
-
-    int base = 0;  // d_i of the running segment lives in d[(base + i) mod 3], i >= -1
-    auto dbuf = [&](long i) { return o.d[(((base + i) % 3) + 3) % 3]; };
-    bool fallback = false;
-    int fails = 0;
-    double prev_true = 0.0;
-    TRY(o.true_residual(x, r, true, true));
-    for (;;) {
-        const double true_err = std::sqrt(h.true_rr);
-        if (o.debug)
-            fprintf(stderr, "[%s] update %d inner %d true %.3e (target %.3e)\n", o.tag, info.reliable_updates, h.k_total,
-                    true_err, tol * h.phi_norm);
-        if (info.reliable_updates > 0) fails = true_err < prev_true ? 0 : fails + 1;
-        prev_true = true_err;
-        if (!(true_err == true_err) || true_err < tol * h.phi_norm || h.k_total >= max_iter) break;
-        if (fails >= 2 || (o.force_fallback && info.reliable_updates >= 1)) {
-            fallback = true;
-            break;
-        }
-        // the segment: pass 0 on the injected direction, then passes 1, 2, ...
-        // until the device ends it; the state is read once per chunk
-        o.inject(r, dbuf(-1), dbuf(0));
-        long j = 0;
-        bool done;
-        TRY(cg_chunked(
-            (long)(max_iter - h.k_total) + 1,  // the device stops itself at max_iter
-            [&](long nb) {
-                for (long i = 0; i < nb; ++i, ++j)  // passes 0 and 1 both read d_0 and d_{-1}; pass 0 stores no d
-                    o.pass(j, j == 0 ? dbuf(0) : dbuf(j - 1), j == 0 ? dbuf(-1) : dbuf(j - 2), dbuf(j));
-                return SM_OK;
-            },
-            [&](CgStatus *st) {
-                TRY(o.read());
-                if (o.debug)
-                    fprintf(stderr, "[%s]   passes %ld k %d err %.3e M %.3e done %d\n", o.tag, j, h.k, h.err, h.M, h.done);
-                *st = CgStatus{h.k, h.err, std::fmax(o.delta * h.M, tol * h.phi_norm), h.done};
-                return SM_OK;
-            },
-            &done));
-        if (!done) return fail(SM_ERR_STATE, "%s", o.stuck);
-        info.inner_iterations = h.k_total;
-        const int J = h.k;
-        if (h.bad) {  // a non-finite scalar: y is not trusted, x and r are those of the last update
-            o.fold(x, dbuf(0), 1);
-            TRY(o.check());
-            fallback = true;
-            break;
-        }
-        o.fold(x, dbuf(J - 1), 0);
-        base = (int)((base + J) % 3);  // d_{J-1} becomes the next segment's d_{-1}, d_J's buffer takes its d_0
-        info.reliable_updates++;
-        TRY(o.true_residual(x, r, false, false));
-    }
-    info.inner_iterations = h.k_total;
-    double true_err = std::sqrt(h.true_rr);
-    const double phi_norm = h.phi_norm;
-    if (fallback && h.k_total < max_iter && true_err > 0.0) {
-        // the fp64 finish: A e = r (r kept apart: the fp64 solver's own buffers may include it)
-        Vec *rhs, *e;
-        TRY(o.finish_vectors(&rhs, &e));
-        o.copy(r, rhs);
-        sm_cg_result r64{};
-        TRY(o.solve64(rhs, e, tol * phi_norm / true_err, max_iter - h.k_total, &r64));
-        o.add(x, e);
-        info.fell_back = 1;
-        info.fp64_iterations = r64.iterations;
-        const int inner = h.k_total;
-        TRY(o.true_residual(x, r, false, true));
-        info.inner_iterations = inner;
-        true_err = std::sqrt(h.true_rr);
-    } else if (fallback) {
-        info.fell_back = 1;
-    }
-    info.true_residual = phi_norm > 0.0 ? true_err / phi_norm : true_err;
-    res->converged = true_err < tol * phi_norm ? 1 : 0;
-    res->iterations = info.inner_iterations + info.fp64_iterations;
-    res->residual = true_err;
-    res->phi_norm = phi_norm;
-    return SM_OK;
-}
-
-// The same scheme for the K <= 64 columns of a batched solve (sm_cgbatchmp.cpp),
-// in rounds: inject for the open columns, passes in chunks until every open
-// column's segment has ended (one CgChunker per column, the longest wish wins,
-// all K scalar blocks read once per chunk), fold, one batched true residual,
-// then cg_mixed_drive's decisions column by column. A column whose segment
-// ended early idles until the round is over; a column that has stopped, or is
-// marked for the fp64 finish, is closed: nothing of it is touched again before
-// the finishes, which run one column at a time after the rounds. Every column
-// therefore takes the decisions cg_mixed_drive would take on it alone.
+// The columns go in rounds: inject for the open columns, passes in chunks until
+// every open column's segment has ended (one CgChunker per column, the longest
+// wish wins, all K scalar blocks read once per chunk: with K = 1 the sequence
+// of cg_chunked), fold, one true residual for the open columns, then the
+// decisions column by column. A column whose segment ended early idles until
+// the round is over; a column that has stopped, or is marked for the fp64
+// finish, is closed: nothing of it is touched again before the finishes, which
+// run one column at a time after the rounds. Every column therefore takes the
+// decisions it would take alone.
 //
-// Columns are named by bit masks (bit b = column b). Ops:
+// Columns are named by bit masks (bit b = column b). Ops supplies every device
+// call, and alone knows which solver it serves:
 //   h(b), info(b)            column b's scalars (host mirror) and report
 //   tol, max_iter, delta, force_fallback, debug, tag, stuck
 //   start()                  x = phi, every column
 //   true_residual(m, init, restart)   r_b = phi_b - A x_b and its scalars for b in m, all K mirrors read back
-//   inject(m)                d_0 = fp32(r) + beta d_prev, into the ring's fixed slots
+//                            (init: the solve's first true residual)
+//   inject(m)                d_0 = fp32(r) + beta d_prev
 //   pass(j, m)               pass j of the round and its scalar step
 //   check(), read()          the launches' error state; that and all K scalar blocks into the mirrors
 //   fold(m, discard)         x += y, y = 0 for b in m (b in discard: y = 0 only)
@@ -240,7 +143,7 @@ int cg_mixed_drive(Ops &o, const Vec *phi, Vec *x, Vec *r, sm_cg_result *res) {
 typedef unsigned long long ColMask;
 
 template <class Ops>
-int cg_mixed_drive_batch(Ops &o, int K, sm_cg_result *res) {
+int cg_mixed_drive(Ops &o, int K, sm_cg_result *res) {
     struct Col {
         int fails = 0;
         double prev_true = 0.0;
@@ -259,7 +162,7 @@ int cg_mixed_drive_batch(Ops &o, int K, sm_cg_result *res) {
     o.start();
     TRY(o.true_residual(open, true, true));
     for (;;) {
-        for (int b = 0; b < K; ++b) {  // the head of cg_mixed_drive's loop
+        for (int b = 0; b < K; ++b) {  // what each open column's last true residual decides
             if (!(open & bit(b))) continue;
             const sm::MPScalars &h = o.h(b);
             sm_cg_mixed_info &info = o.info(b);
@@ -346,6 +249,64 @@ int cg_mixed_drive_batch(Ops &o, int K, sm_cg_result *res) {
         res[b].phi_norm = phi_norm;
     }
     return SM_OK;
+}
+
+// A one-column solver's operations as the driver's K = 1 column set. The
+// wrapped Ops (sm_ctx.h MixedDev and what sm_cgmp.cpp / sm_eomp.cpp add):
+//   h, info, d[3]            the scalars' host mirror, the solve's report, the direction buffers
+//   tol, max_iter, delta, force_fallback, debug, tag, stuck
+//   copy(a, b), add(x, e)    b = a, x += e in fp64
+//   true_residual(x, r, init, restart)   r = phi - A x, its scalars into h
+//   inject(r, dprev, d0)     d0 = fp32(r) + beta dprev
+//   pass(j, d1, d2, dn)      pass j of the segment and its scalar step
+//   check(), read()          the launches' error state; that and the scalars into h
+//   fold(x, dlast, discard)  the reliable update's x += y, y = 0 (discard: y = 0 only)
+//   finish_vectors(&rhs, &e), solve64(rhs, e, tol, max_iter, &res)   the fp64 finish
+// The three direction buffers rotate by pointer: d_i of the running segment
+// lives in d[(base + i) mod 3], i >= -1.
+template <class Ops, class Vec>
+struct MixedColumn {
+    Ops &o;
+    const Vec *phi;
+    Vec *x, *r;
+    int base = 0;
+    double tol = o.tol, delta = o.delta;
+    int max_iter = o.max_iter, force_fallback = o.force_fallback, debug = o.debug;
+    const char *tag = o.tag, *stuck = o.stuck;
+
+    auto dbuf(long i) const { return o.d[(((base + i) % 3) + 3) % 3]; }
+    const sm::MPScalars &h(int) const { return o.h; }
+    sm_cg_mixed_info &info(int) { return o.info; }
+    void start() {
+        if (x != phi) o.copy(phi, x);
+    }
+    int true_residual(ColMask, bool init, bool restart) { return o.true_residual(x, r, init, restart); }
+    void inject(ColMask) { o.inject(r, dbuf(-1), dbuf(0)); }
+    void pass(long j, ColMask) {  // passes 0 and 1 both read d_0 and d_{-1}; pass 0 stores no d
+        o.pass(j, j == 0 ? dbuf(0) : dbuf(j - 1), j == 0 ? dbuf(-1) : dbuf(j - 2), dbuf(j));
+    }
+    int check() { return o.check(); }
+    int read() { return o.read(); }
+    void fold(ColMask, ColMask discard) {
+        if (discard) return o.fold(x, dbuf(0), 1);
+        const int J = o.h.k;
+        o.fold(x, dbuf(J - 1), 0);
+        base = (base + J) % 3;  // d_{J-1} becomes the next segment's d_{-1}, d_J's buffer takes its d_0
+    }
+    int finish(int, double tol64, int iters, sm_cg_result *r64) {  // r kept apart: the fp64 solver's own buffers may include it
+        Vec *rhs, *e;
+        TRY(o.finish_vectors(&rhs, &e));
+        o.copy(r, rhs);
+        TRY(o.solve64(rhs, e, tol64, iters, r64));
+        o.add(x, e);
+        return SM_OK;
+    }
+};
+
+template <class Ops, class Vec>
+int cg_mixed_drive(Ops &o, const Vec *phi, Vec *x, Vec *r, sm_cg_result *res) {
+    MixedColumn<Ops, Vec> col{o, phi, x, r};
+    return cg_mixed_drive(col, 1, res);
 }
 
 }  // namespace sm_host

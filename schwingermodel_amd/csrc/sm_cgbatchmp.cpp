@@ -1,10 +1,11 @@
 // sm_cgbatchmp.cpp -- mixed-precision batched CG on D D^dagger: fp32 inner
 // iterations for K columns in one launch per pass (sm_cgbatchsp.hip) held to
 // the fp64 stop test, column by column, by reliable updates. The scheme and its
-// driver are sm_cg_host.h's cg_mixed_drive_batch; here are the batch's
-// operations for it: the true residual through two launch_batch_apply, the fp32
-// pass, the injection into the ring's fixed slots, the fold, and the fp64
-// batched solver with K = 1 as a column's finish.
+// driver are sm_cg_host.h's cg_mixed_drive, the one the one-column solvers
+// enter with K = 1; here are the batch's operations for it: the true residual
+// through two launch_batch_apply, the fp32 pass, the injection into the ring's
+// fixed slots, the fold, and the fp64 batched solver with K = 1 as a column's
+// finish.
 //
 // One-shard contexts only (sm_cg_batch_precision refuses the others).
 // Everything the fp32 side touches is its own (btmp of sm_ctx), so the fp64
@@ -157,7 +158,7 @@ int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, 
     launch_sp_convert_links(c->stream, c->g, c->U, c->btmp.U);
     HIP_TRY(hipGetLastError());
     BatchOps ops{c, c->btmp, K, phi, x, m0, tol, max_iter, cg_batch_config(c->g, K, c->bt_tiles)};
-    return cg_mixed_drive_batch(ops, K, res);
+    return cg_mixed_drive(ops, K, res);
 }
 
 }  // namespace sm_host

@@ -1,8 +1,9 @@
 // sm_cgmp.cpp -- mixed-precision CG on D D^dagger: fp32 inner iterations
 // (sm_cgsp.hip, two-direction passes) held to the fp64 stop test by reliable
-// updates. The scheme and its driver are sm_cg_host.h's cg_mixed_drive; here
-// are the full lattice's operations for it: the true residual through the
-// existing fp64 apply, the fp32 pass, the fold and cg_dev_fp64 as the finish.
+// updates. The scheme and its driver are sm_cg_host.h's cg_mixed_drive, which
+// this solver enters as one column (MixedColumn); here are the full lattice's
+// operations for it: the true residual through the existing fp64 apply, the
+// fp32 pass, the fold and cg_dev_fp64 as the finish.
 //
 // One-shard contexts only (sm_cg_precision refuses the others). Everything the
 // fp32 side touches is its own -- directions, y, links, partials, scalars --

@@ -340,8 +340,9 @@ int placement_probe_default();            // candidates per buffer for new conte
 int cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 int cg_dev_mixed(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 void mixed_free(sm_ctx *c, MixedWs &w);  // either mixed solver's state
-// The device calls of cg_mixed_drive (sm_cg_host.h) that do not depend on the
-// operator. A solver adds true_residual, pass, fold and solve64 on its own.
+// The device calls of a one-column mixed solve (sm_cg_host.h MixedColumn) that
+// do not depend on the operator. A solver adds true_residual, pass, fold and
+// solve64 on its own.
 struct MixedDev {
     sm_ctx *c;
     MixedWs &w;

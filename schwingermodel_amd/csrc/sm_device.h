@@ -1,6 +1,7 @@
 // sm_device.h -- device-side helpers shared by the gfx950 kernels:
 // std::complex<double> arithmetic with GCC's exact semantics (no contraction),
-// the Wilson-Dirac site stencil, deterministic block reduction, DPP lane shifts.
+// the Wilson-Dirac site stencil, deterministic block reduction, DPP lane shifts,
+// the scalar steps and fp32 primitives of the mixed-precision passes.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -363,6 +364,65 @@ __device__ __forceinline__ void mp_update_step(MPScalars *sc, double2 s, int ini
     sc->k = 0;
     sc->bad = 0;
     sc->done = err < sc->tol * sc->phi_norm || sc->k_total >= sc->max_iter || !finite_d(s.x) ? 1 : 0;
+}
+
+// ---- fp32 primitives of the mixed-precision passes (the same three files) ----
+struct Spf {  // a 2-spinor at one site, fp32
+    float2 a, b;
+};
+__device__ __forceinline__ float dppf_shr1(float v) {  // lane l <- lane l-1, lane 0 gets 0
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float dppf_shl1(float v) {  // lane l <- lane l+1, lane 63 gets 0
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float2 f2(float x, float y) { return make_float2(x, y); }
+__device__ __forceinline__ float2 addf(float2 a, float2 b) { return f2(a.x + b.x, a.y + b.y); }
+__device__ __forceinline__ float2 subf(float2 a, float2 b) { return f2(a.x - b.x, a.y - b.y); }
+__device__ __forceinline__ float2 negf(float2 a) { return f2(-a.x, -a.y); }
+__device__ __forceinline__ float2 mulif(float2 z) { return f2(-z.y, z.x); }
+__device__ __forceinline__ float2 mulmif(float2 z) { return f2(z.y, -z.x); }
+__device__ __forceinline__ float2 cmf(float2 a, float2 b) {  // a b
+    return f2(__fmaf_rn(a.x, b.x, -(a.y * b.y)), __fmaf_rn(a.x, b.y, a.y * b.x));
+}
+__device__ __forceinline__ float2 axpyf(float s, float2 a, float2 c) {  // c + s a
+    return f2(__fmaf_rn(s, a.x, c.x), __fmaf_rn(s, a.y, c.y));
+}
+// acc + Re(a conj b), the products and the sum in fp64
+__device__ __forceinline__ double dacc(double acc, float2 a, float2 b) {
+    return __builtin_fma((double)a.x, (double)b.x, __builtin_fma((double)a.y, (double)b.y, acc));
+}
+
+// D (DAG = 0) / D^dag (DAG = 1) at this lane's column (sm_cgsp.hip,
+// sm_cgbatchsp.hip), sm_cgra.hip ra_site FOLD = 2: centre p, x-neighbours
+// pxm / pxp, t-neighbours from the adjacent lanes (one complex per hop), links
+// pre-scaled so the bracket's terms come out as -h/2's and the output is one fma.
+template <int DAG>
+__device__ __forceinline__ Spf sp_site(float mass, const Spf &p, const Spf &pxm, const Spf &pxp, float2 ut, float2 ux,
+                                       float2 uxm) {
+    const float2 qf = DAG ? addf(p.a, p.b) : subf(p.a, p.b);
+    const float2 qb = DAG ? subf(p.a, p.b) : addf(p.a, p.b);
+    const float2 bp = cmf(f2(ut.x, -ut.y), qb);
+    const float2 C = f2(dppf_shr1(bp.x), dppf_shr1(bp.y));   // lane t-1's backward product (its sign included)
+    const float2 qt = f2(dppf_shl1(qf.x), dppf_shl1(qf.y));  // lane t+1's forward combination
+    const float2 A = cmf(ut, qt);
+    const float2 e = f2(uxm.x, -uxm.y);
+    float2 h0, h1;
+    if (!DAG) {
+        const float2 B = cmf(ux, f2(pxp.a.x - pxp.b.y, pxp.a.y + pxp.b.x));
+        const float2 E = cmf(e, f2(pxm.a.x + pxm.b.y, pxm.a.y - pxm.b.x));
+        h0 = addf(addf(addf(A, B), C), E);
+        h1 = addf(addf(addf(negf(A), mulmif(B)), C), mulif(E));
+    } else {
+        const float2 E = cmf(e, f2(pxm.a.x - pxm.b.y, pxm.a.y + pxm.b.x));
+        const float2 B = cmf(ux, f2(pxp.a.x + pxp.b.y, pxp.a.y - pxp.b.x));
+        h0 = addf(addf(addf(C, E), A), B);
+        h1 = addf(addf(addf(negf(C), mulmif(E)), A), mulif(B));
+    }
+    Spf o;
+    o.a = axpyf(mass, p.a, h0);
+    o.b = axpyf(mass, p.b, h1);
+    return o;
 }
 
 // A block-uniform double2 (e.g. read back from LDS) into scalar registers.

@@ -1,8 +1,9 @@
 // sm_eomp.cpp -- mixed-precision CG on Dhat Dhat^dagger (the even-odd
 // action's solver): fp32 inner iterations (sm_eosp.hip, the stored-Ad one-pass
 // kernel on half-lattice vectors) held to the fp64 stop test by reliable
-// updates. The scheme and its driver are sm_cg_host.h's cg_mixed_drive; here
-// are the even-odd operations for it: the true residual through eo_dhat, the
+// updates. The scheme and its driver are sm_cg_host.h's cg_mixed_drive, which
+// this solver enters as one column (MixedColumn); here are the even-odd
+// operations for it: the true residual through eo_dhat, the
 // fp32 pass with its two Ad buffers, the fold (which adds alpha_{J-1} d_{J-1}
 // after an odd last pass J) and eo_cg as the finish.
 //

@@ -36,7 +36,9 @@
 // term carries one link, so a hop's bracket comes out as -H/2: the odd hop
 // T = D_oe v is the bracket itself and Dhat v = m v - (1/m) bracket(T).
 //
-// One float2 per lane; a two-column-per-lane form was not built.
+// One float2 per lane; a two-column-per-lane form was not built. The fp32
+// arithmetic below the bracket (Spf, the DPP float shifts, the float2 helpers,
+// dacc) is sm_device.h's, shared with sm_cgsp.hip and sm_cgbatchsp.hip.
 #include <type_traits>
 
 #include "sm_device.h"
@@ -51,10 +53,6 @@ namespace {
 constexpr int EW = kEoTdWaveCols;  // owned k-columns per wave
 constexpr int EH = 4;              // halo lanes per side: one per hop
 
-struct Spf {  // a 2-spinor at one site, fp32
-    float2 a, b;
-};
-
 struct EoSPArgs {
     const float2 *d1, *d2, *aold;  // d_{j-1}, d_{j-2}, Ad_{j-1}
     float2 *dn, *anew, *y;
@@ -66,29 +64,6 @@ struct EoSPArgs {
     int xchunk, NWT, TBk, XB;
     float mass, imass;             // m, 1 / m
 };
-
-__device__ __forceinline__ float dppf_shr1(float v) {  // lane l <- lane l-1, lane 0 gets 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float dppf_shl1(float v) {  // lane l <- lane l+1, lane 63 gets 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float2 f2(float x, float y) { return make_float2(x, y); }
-__device__ __forceinline__ float2 addf(float2 a, float2 b) { return f2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 subf(float2 a, float2 b) { return f2(a.x - b.x, a.y - b.y); }
-__device__ __forceinline__ float2 negf(float2 a) { return f2(-a.x, -a.y); }
-__device__ __forceinline__ float2 mulif(float2 z) { return f2(-z.y, z.x); }
-__device__ __forceinline__ float2 mulmif(float2 z) { return f2(z.y, -z.x); }
-__device__ __forceinline__ float2 cmf(float2 a, float2 b) {  // a b
-    return f2(__fmaf_rn(a.x, b.x, -(a.y * b.y)), __fmaf_rn(a.x, b.y, a.y * b.x));
-}
-__device__ __forceinline__ float2 axpyf(float s, float2 a, float2 c) {  // c + s a
-    return f2(__fmaf_rn(s, a.x, c.x), __fmaf_rn(s, a.y, c.y));
-}
-// acc + Re(a conj b), the products and the sum in fp64
-__device__ __forceinline__ double dacc(double acc, float2 a, float2 b) {
-    return __builtin_fma((double)a.x, (double)b.x, __builtin_fma((double)a.y, (double)b.y, acc));
-}
 
 // One checkerboard hop's bracket (sm_eotd.hip eo_bracket) with pre-scaled,
 // signed links: at a lane whose forward t-neighbour is lane+1 and backward one

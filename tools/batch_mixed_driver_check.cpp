@@ -1,5 +1,5 @@
-// batch_mixed_driver_check.cpp -- the decisions of the batched mixed-precision solver's
-// K-column reliable-update driver (csrc/sm_cg_host.h cg_mixed_drive_batch) under the host
+// batch_mixed_driver_check.cpp -- the decisions of the mixed-precision solvers'
+// reliable-update driver (csrc/sm_cg_host.h cg_mixed_drive) on K columns under the host
 // sanitizers: no device, the operations are a script per column.
 //
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude
@@ -7,9 +7,11 @@
 //
 // Every column has its own script: the fp64 true residuals, and each segment's k, done and
 // bad (tools/mixed_driver_check.cpp's). The batch is driven with all K scripts at once, and
-// each script alone through cg_mixed_drive: a column's result, report and the sequence of
-// its own operations (true residuals, injections, folds, the fp64 finish and what it is
-// given) must be the same. The scripted device ends a column's segment on that column's
+// each script alone as a one-column solver's operations through MixedColumn: a column's
+// result, report and the sequence of its own operations (true residuals, injections, folds,
+// the fp64 finish and what it is given) must be the same. Both sides run the one driver, so
+// this pins that a column is not touched by its neighbours; what the decisions are on a
+// column alone is tools/mixed_driver_check.cpp's to assert. The scripted device ends a column's segment on that column's
 // script alone and never changes a column that is not named in an operation's mask, which
 // the checks assert. Covered: segments that end at different passes with the early ones
 // idling, a column that converges at the first update while others go on, a bad column
@@ -102,7 +104,7 @@ struct Column {
     }
 };
 
-// cg_mixed_drive's operations on one Column: the script alone.
+// A one-column solver's operations (MixedColumn's Ops) on one Column: the script alone.
 struct Vec { int dummy; };
 struct Dir { int id; };
 struct LoneOps {
@@ -210,7 +212,7 @@ static BatchOps compare(const std::vector<Script> &scripts, int max_iter = 1000,
         o.cols.push_back(c);
     }
     std::vector<sm_cg_result> res((size_t)K);
-    CHECK(sm_host::cg_mixed_drive_batch(o, K, res.data()) == SM_OK);
+    CHECK(sm_host::cg_mixed_drive(o, K, res.data()) == SM_OK);
     for (int b = 0; b < K; ++b) {
         LoneOps l;
         l.c.s = scripts[(size_t)b];
@@ -315,8 +317,8 @@ static void check_k1_and_k64() {
     CHECK(p.pass_masks[0] == ~(ColMask)0 && p.cols[63].info.fell_back == 1 && p.cols[62].info.fell_back == 0);
     std::vector<sm_cg_result> res(65);
     BatchOps z;
-    CHECK(sm_host::cg_mixed_drive_batch(z, 0, res.data()) == SM_ERR_ARG);
-    CHECK(sm_host::cg_mixed_drive_batch(z, 65, res.data()) == SM_ERR_ARG);
+    CHECK(sm_host::cg_mixed_drive(z, 0, res.data()) == SM_ERR_ARG);
+    CHECK(sm_host::cg_mixed_drive(z, 65, res.data()) == SM_ERR_ARG);
 }
 
 static void check_endless_segment() {  // a device that never ends a segment is an error, not a hang
@@ -331,7 +333,7 @@ static void check_endless_segment() {  // a device that never ends a segment is 
     c.s = Script{{1}, {{5, 0}}};
     o.cols.push_back(c);
     sm_cg_result res{};
-    CHECK(sm_host::cg_mixed_drive_batch(o, 1, &res) == SM_ERR_STATE);
+    CHECK(sm_host::cg_mixed_drive(o, 1, &res) == SM_ERR_STATE);
     CHECK(last_error == o.stuck && o.issued == 41);
 }
 

@@ -1,6 +1,6 @@
 // mixed_driver_check.cpp -- the decisions of the mixed-precision solvers' reliable-update
-// driver (csrc/sm_cg_host.h cg_mixed_drive) under the host sanitizers: no device, the
-// operations are a script.
+// driver (csrc/sm_cg_host.h cg_mixed_drive) on one column, as the one-column solvers reach
+// it (through MixedColumn), under the host sanitizers: no device, the operations are a script.
 //
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude
 //       tools/mixed_driver_check.cpp -o build/mixed_driver_check && build/mixed_driver_check
@@ -9,8 +9,8 @@
 // from lists, hand out three tagged direction buffers and log every call. Covered: the
 // plain solve, the two-failed-updates fallback and what the fp64 finish is given, the bad
 // segment, the iteration limit in a segment and after a forced fallback, the NaN true
-// residual, the segment that never ends, and the buffer rotation across segments of
-// lengths 1, 2, 4, 5. tol 1e-10, |phi| = 1 throughout.
+// residual, the segment that never ends, the buffer rotation across segments of lengths
+// 1, 2, 4, 5, and the start in place (x == phi: no copy). tol 1e-10, |phi| = 1 throughout.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -287,6 +287,24 @@ static void check_rotation() {  // 8
     }
 }
 
+static void check_in_place() {  // 9: x == phi starts without a copy, x != phi with exactly one
+    Ops o;
+    o.true_r = {1, 1e-4, 1e-11};
+    o.segs = {{9, 0, 0}, {14, 0, 0}};
+    sm_cg_result res{};
+    CHECK(sm_host::cg_mixed_drive(o, &phi, &phi, &r, &res) == SM_OK);
+    CHECK(o.count("copy phi phi") == 0 && o.calls.front() == "true restart");
+    Ops p;
+    p.true_r = o.true_r;
+    p.segs = o.segs;
+    sm_cg_result res2;
+    CHECK(run(p, &res2) == SM_OK);
+    CHECK(p.count("copy phi x") == 1 && p.calls.front() == "copy phi x");
+    CHECK(std::vector<std::string>(p.calls.begin() + 1, p.calls.end()) == o.calls);  // nothing else differs
+    CHECK(res.converged == 1 && res.iterations == res2.iterations && res.residual == res2.residual);
+    CHECK(o.info.reliable_updates == 2 && o.info.inner_iterations == 23);
+}
+
 int main() {
     check_plain();
     check_two_failed_updates();
@@ -296,6 +314,7 @@ int main() {
     check_nan();
     check_endless_segment();
     check_rotation();
+    check_in_place();
     if (failures) {
         std::fprintf(stderr, "mixed_driver_check: %d failures\n", failures);
         return 1;
