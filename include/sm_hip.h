@@ -591,6 +591,46 @@ int sm_cg_batch_mixed_last(const sm_ctx *ctx, int K, sm_cg_mixed_info *out /* K 
 int sm_pion_correlator(sm_ctx *ctx, double m0, double tol, int max_iter, int nsrc, const int *src_x,
                        const int *src_t, double *C /* nsrc*Nt, host */, sm_cg_result *res /* 2*nsrc, nullable */);
 
+/* ==== batched even-odd CG ====================================================
+ * Dhat Dhat^dag x_b = phi_b on the even sites for K right-hand sides on the
+ * context's current gauge field, ONE launch per iteration for the whole batch
+ * (schwingermodel_amd/csrc/sm_eobatch.hip): the batched counterpart of
+ * sm_eo_cg_dev. Each column runs the one-pass even-odd iteration of
+ * sm_eo_cg's default path (the two-direction recurrence, both Dhat^dag and
+ * Dhat in one march) with its own alpha, beta, residual and stop test
+ * ||r_b|| < tol ||phi_b,e||; a column that has stopped costs nothing more. A
+ * column's result depends on its own source, the gauge field, m0, tol and
+ * max_iter only: bitwise the same alone, at any position of any batch and
+ * next to any other columns.
+ * Layout: K full-layout columns as in sm_cg_batch. The even part of phi_b
+ * ((x + t) even) is the source, its odd part is ignored; x_b's odd sites are
+ * set to 0. x must not alias phi. res[b] reports column b as sm_cg_result
+ * reports a lone sm_eo_cg_dev. Returns SM_OK also when some columns reach
+ * max_iter. SM_ERR_ARG for K < 1, K > sm_cg_batch_max(), a null pointer, x
+ * aliasing phi, max_iter < 0, odd Nx or Nt, and on sharded, host-staged,
+ * loopback and peer contexts; SM_ERR_STATE before a gauge upload; SM_ERR_HIP
+ * when an allocation fails (sm_last_error() names the bytes asked for; the
+ * context stays usable).
+ * Always fp64: sm_cg_precision, sm_eo_cg_precision and sm_cg_batch_precision
+ * do not reach it.
+ * Traffic per even site and column: ~256 B per iteration (sm_eotd.hip's).
+ * Memory, allocated at the first call, regrown for a larger K and freed by
+ * sm_destroy: three direction and two Ad buffers on the half lattice (80 B per
+ * site and column), the columns' even parts (32 B per site and column; the
+ * host-pointer entry stages phi and x on the device: 64 B more), the
+ * checkerboard copy of the gauge field (32 B per site), partial sums (48 B per
+ * column and (56 k-columns x G rows), G = 2 below Nx = 512, 8 from there) and
+ * one scalar block per column. It shares no buffer or state with sm_eo_cg /
+ * sm_eo_cg_dev, the mixed solvers, sm_cg_batch or the stepwise solver; the
+ * checkerboard links are rebuilt from the current gauge field at every call,
+ * so an upload or an HMC trajectory between two solves needs no call.
+ * Synchronous. */
+int sm_eo_cg_batch_dev(sm_ctx *ctx, int K, const double *phi, double *x, double m0, double tol, int max_iter,
+                       sm_cg_result *res /* K */);
+/* The same with host pointers. */
+int sm_eo_cg_batch(sm_ctx *ctx, int K, const double *phi, double *x, double m0, double tol, int max_iter,
+                   sm_cg_result *res /* K */);
+
 /* ==== replica ensemble: R independent HMC chains, one launch per step ========
  * R <= sm_ens_max() gauge fields in one context, evolved in lockstep: every CG
  * iteration and every molecular-dynamics kernel is ONE launch for all replicas
@@ -598,8 +638,8 @@ int sm_pion_correlator(sm_ctx *ctx, double m0, double tol, int max_iter, int nsr
  * is bound by launch latency (11-12 us per CG iteration whatever the lattice);
  * R chains -- more statistics, or one chain per (beta, m0) point of a scan --
  * share that cost. Replica r has its own m0, beta, tau and seed; md_steps,
- * cg_tol and cg_max_iter are common (the replicas share every launch) and
- * even_odd must be 0: anything else is SM_ERR_ARG naming the field.
+ * cg_tol, cg_max_iter and even_odd (0 or 1) are common (the replicas share
+ * every launch): anything else is SM_ERR_ARG naming the field.
  * sm_ens_hmc_trajectory is HMC::HMC_Update (src/hmc.cpp:151-178) for every
  * replica at once: the draws, phi = D chi, H_old (one batched solve of R
  * columns, column r on replica r's links and mass), the leapfrog with the
@@ -628,8 +668,23 @@ int sm_pion_correlator(sm_ctx *ctx, double m0, double tol, int max_iter, int nsr
  * while some replica has no gauge field; SM_ERR_HIP (sm_last_error() names the
  * bytes asked for) when an allocation fails, after which the context stays
  * usable. Synchronous.
- * Not in this version: t-sharded ensembles, the even-odd action, mixed
- * precision, the sm_hmc program. */
+ * even_odd = 1 for every replica: replica r does what sm_hmc_trajectory does
+ * with even_odd = 1 and p[r] -- the same draws, phi_e = Dhat chi_e, H =
+ * kinetic + gauge + Re <X, phi_e> with X from ONE batched even-odd solve of R
+ * columns on the replicas' own links and masses (sm_eo_cg_batch's solver), the
+ * force from the bilinear of l = (X, (1/2m) H'_oe X) and r = (Y, (1/2m) H_oe Y),
+ * Y = Dhat^dag X. It samples the same gauge distribution with about 0.4x the
+ * CG iterations. What is said above about bitwise independence, the draws, sp
+ * and gauge_action, rejected replicas and the agreement with a lone chain
+ * holds for it too. Odd Nx or Nt with even_odd = 1 is SM_ERR_ARG (an odd
+ * periodic lattice has no checkerboard); the ensemble stays usable for the
+ * plain action, whose path and results do not change, and plain and even-odd
+ * trajectories may alternate on one ensemble. The even-odd fields are
+ * allocated at the first even-odd trajectory, not by sm_ens_create: 208 B per
+ * site and replica (checkerboard links 32, six half-lattice fields 96, the
+ * batched even-odd solver's workspace 80).
+ * Not in this version: t-sharded ensembles, mixed precision, the sm_hmc
+ * program. */
 typedef struct sm_ens sm_ens;
 int sm_ens_max(void);   /* = sm_cg_batch_max() */
 int sm_ens_create(sm_ctx *ctx, int R, sm_ens **out);   /* allocates all fields */

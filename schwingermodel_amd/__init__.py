@@ -202,6 +202,24 @@ class Lattice:
         self._batch_K = K
         return x, list(res)
 
+    def eo_cg_batch(self, phi, m0, tol=None, max_iter=None):
+        """Solve Dhat Dhat^dagger x_b = phi_b,e on the even sites for K
+        right-hand sides on the context's current gauge field in one batched
+        solve (sm_eo_cg_batch; no implicit upload). phi: complex128 of shape
+        (K, 2, V) in the full layout, its even part is the source. Returns
+        (x, [CGResult] * K); x is zero on the odd sites. Always fp64."""
+        if not isinstance(phi, np.ndarray) or phi.dtype != np.complex128:
+            raise TypeError("eo_cg_batch: phi must be a complex128 numpy array")
+        if phi.ndim != 3 or phi.shape[1:] != (2, self.V) or phi.shape[0] < 1:
+            raise ValueError(f"eo_cg_batch: phi has shape {phi.shape}, expected (K, 2, {self.V})")
+        K = phi.shape[0]
+        phi = np.ascontiguousarray(phi)
+        x = np.empty_like(phi)
+        res = (CGResult * K)()
+        check(lib.sm_eo_cg_batch(self.ctx, K, _vp(phi), _vp(x), float(m0), float(CG.tol if tol is None else tol),
+                                 int(CG.max_iter if max_iter is None else max_iter), res))
+        return x, list(res)
+
     def pion_correlator(self, m0, sources, tol=None, max_iter=None):
         """Pion correlator from point sources on the context's current gauge
         field (sm_pion_correlator; no implicit upload). sources: a list of
@@ -288,8 +306,8 @@ class Ensemble:
             for name in ("md_steps", "cg_tol", "cg_max_iter"):
                 if getattr(p, name) != getattr(params[0], name):
                     raise ValueError(f"ensemble: {name} must be the same for every replica")
-            if p.even_odd != 0:
-                raise ValueError("ensemble: even_odd must be 0")
+            if p.even_odd not in (0, 1) or p.even_odd != params[0].even_odd:
+                raise ValueError("ensemble: even_odd must be 0 or 1 and the same for every replica")
         return (HMCParams * self.R)(*params)
 
     def upload_gauge(self, r, U):

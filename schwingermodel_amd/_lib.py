@@ -147,6 +147,8 @@ def _load():
         "sm_cg_batch_max": ([], ci),
         "sm_cg_batch_dev": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
         "sm_cg_batch": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
+        "sm_eo_cg_batch_dev": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
+        "sm_eo_cg_batch": ([vp, ci, vp, vp, cd, cd, ci, ctypes.POINTER(CGResult)], ci),
         "sm_cg_batch_precision": ([vp, ci, ctypes.POINTER(ci)], ci),
         "sm_cg_batch_mixed_last": ([vp, ci, ctypes.POINTER(CGMixedInfo)], ci),
         "sm_pion_correlator": ([vp, cd, cd, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp,

@@ -261,6 +261,7 @@ int sm_comm_unique_id(void *id_out, int id_bytes) {
 //   link_angles=0|1     recompute-Ad pass reads the links as one-double codes
 //   ra_xchunk=N         recompute-Ad pass: N rows per tile (with ra_xbal=1: ceil(Nx/N) balanced chunks)
 //   batch_tiles=N       batched CG (sm_cgbatch.cpp, sm_cgbatchmp.cpp): tiles per launch the tile height aims at
+//   eo_batch_tiles=N    batched even-odd CG (sm_eobatch.cpp): tiles per launch the tile height aims at
 //   kernel_events=0|1   t-shard CG pass: hand-offs between the streams on events
 //                       recorded by the launches themselves (1, the default) or markers
 //   bt=64|128|256       Dirac apply t-columns per block
@@ -331,6 +332,9 @@ static int apply_test_opts(sm_ctx *c) {
         } else if (k == "batch_tiles") {  // batched CG: tiles per launch the tile height aims at
             if (iv < 1) return fail(SM_ERR_ARG, "SM_TEST_OPTS: batch_tiles must be >= 1");
             c->bt_tiles = iv;
+        } else if (k == "eo_batch_tiles") {  // batched even-odd CG: tiles per launch the tile height aims at
+            if (iv < 1) return fail(SM_ERR_ARG, "SM_TEST_OPTS: eo_batch_tiles must be >= 1");
+            c->eob_tiles = iv;
         } else if (k == "ra_xbal") {
             c->racfg.xbal = iv ? 1 : 0;
         } else if (k == "ra_remap") {
@@ -621,6 +625,7 @@ int sm_destroy(sm_ctx *c) {
     mixed_free(c, c->eomp);
     cg_batch_free(c);
     cg_batch_mixed_free(c);
+    eo_batch_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};

@@ -50,6 +50,17 @@ struct CGBatchWs {
     sm::CGScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
 };
 
+// Workspace of a batched even-odd CG solve of up to K columns (sm_eobatch.cpp),
+// half-lattice vectors of V complex per column: the context owns one for
+// sm_eo_cg_batch, a replica ensemble its own.
+struct EoBatchWs {
+    int K = 0;                      // columns it holds
+    double2 *d[3] = {};             // d_i in d[i mod 3], K x V complex each
+    double2 *a[2] = {};             // Ad by pass parity
+    double2 *partials = nullptr;    // K x EoBatchCfg::pstride
+    sm::CGScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
+};
+
 // State of a mixed-precision solver (sm_cgmp.cpp on the full lattice,
 // sm_eomp.cpp on one parity): its own directions, y, links, partials and
 // scalars, from the first mixed solve on; nothing shared with the fp64 paths.
@@ -261,6 +272,18 @@ struct sm_ctx {
     int *bt_src = nullptr;          // 2 x kBatchMax / 2 ints
     double *bt_C = nullptr;         // kBatchMax / 2 x Wt
 
+    // batched even-odd CG (sm_eobatch.cpp; one shard, fp64): its own workspace
+    // for eob.K columns, the checkerboard copy of U it makes at every call, the
+    // columns' even parts (eob_K columns) and the host-pointer entry's
+    // full-layout staging (eob_fK columns), all from the first call on. Shares
+    // nothing with eo / Ucb, the mixed solvers, bt or the stepwise solver.
+    EoBatchWs eob;
+    int eob_tiles = 0;              // test option eo_batch_tiles=N: tiles per launch aimed at (0: kEoBatchTargetTiles)
+    double2 *eob_U = nullptr;       // even links, then odd links: 2V complex
+    int eob_K = 0, eob_fK = 0;
+    double2 *eob_phi = nullptr, *eob_x = nullptr;    // eob_K x V complex
+    double2 *eob_fphi = nullptr, *eob_fx = nullptr;  // eob_fK x 2V complex
+
     double2 *field(int i) { return fields[i]; }
 };
 
@@ -395,6 +418,16 @@ int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, dou
 int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
                    sm_cg_result *res);
 void cg_batch_mixed_free(sm_ctx *c);
+
+// The batched even-odd CG (sm_eobatch.cpp): a workspace for K columns on c's
+// lattice (zeroed; SM_ERR_HIP names the bytes on failure and leaves w empty),
+// and the solve on any such workspace: K even vectors phi -> x (V complex
+// apart), column b on l's checkerboard links and mass.
+void eo_batch_free(sm_ctx *c);
+int eo_batch_ws_alloc(sm_ctx *c, EoBatchWs &w, int K);
+void eo_batch_ws_free(EoBatchWs &w);
+int eo_batch_solve(sm_ctx *c, const EoBatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
+                   double tol, int max_iter, sm_cg_result *res);
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

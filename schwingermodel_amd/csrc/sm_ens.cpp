@@ -18,9 +18,16 @@
 //            launch and read with one synchronisation per Hamiltonian.
 //   draws    replica r's are those of a lone chain with p[r].seed.
 //
-// One-shard contexts, the plain (not even-odd) action, always fp64. Kernels:
-// sm_gauge.hip, sm_kernels.hip (ens_*), sm_cgbatch.hip. Host bookkeeping that
-// needs no device: sm_ens_host.h.
+//   even-odd the action phi_e^dag (Dhat Dhat^dag)^-1 phi_e of sm_eo.cpp when every
+//            replica asks for it: the checkerboard links of all slabs are
+//            rebuilt before every solve (one launch), X comes from one batched
+//            even-odd solve (sm_eobatch.cpp), Dhat chi, Dhat^dag X and the odd
+//            parts of l and r from batched checkerboard hops. Its fields are
+//            allocated at the first even-odd trajectory.
+//
+// One-shard contexts, always fp64. Kernels: sm_gauge.hip, sm_kernels.hip
+// (ens_*), sm_cgbatch.hip, sm_eobatch.hip. Host bookkeeping that needs no
+// device: sm_ens_host.h.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -46,6 +53,10 @@ struct sm_ens {
     double2 *part = nullptr;                                // 3 x R x gauge_reduce_blocks partials
     double2 *sums = nullptr, *h_sums = nullptr;             // 3 x R
     std::vector<char> have;                                 // replica r holds a gauge field
+    // even-odd action, from the first even-odd trajectory on
+    EoBatchWs eows;
+    double2 *Ucb = nullptr;                                 // even links R x V complex, then odd links R x V
+    double2 *eh = nullptr;                                  // EH_N half-lattice fields, R x V complex each
 };
 
 namespace {
@@ -57,14 +68,21 @@ struct HTerms {
 
 size_t slab_complex(const sm_ens *e) { return 2 * (size_t)e->c->g.V; }
 
+// half-lattice fields of the even-odd action: phi_e, X, Y = Dhat^dag X, the odd
+// work field of Dhat, l_o (chi_e during the heat bath), r_o
+enum { EH_PHI, EH_X, EH_Y, EH_T, EH_LO, EH_RO, EH_N };
+double2 *eh(const sm_ens *e, int i) { return e->eh + (size_t)i * (size_t)e->R * (size_t)e->c->g.V; }
+
 void ens_free(sm_ens *e) {
-    void *dev[] = {e->U, e->Ubak, e->chi, e->phi, e->x, e->P, e->F, e->par, e->massv, e->part, e->sums};
+    void *dev[] = {e->U, e->Ubak, e->chi, e->phi, e->x,   e->P,  e->F,
+                   e->par, e->massv, e->part, e->sums, e->Ucb, e->eh};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     void *host[] = {e->h_par, e->h_mass, e->h_sums};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     cg_batch_ws_free(e->ws);
+    eo_batch_ws_free(e->eows);
     delete e;
 }
 
@@ -92,6 +110,38 @@ int all_have(const sm_ens *e) {
 
 BatchLinks links(const sm_ens *e) { return BatchLinks{e->U, (long)slab_complex(e), 0.0, e->massv}; }
 
+EoBatchLinks eo_links(const sm_ens *e) {
+    const long V = e->c->g.V;
+    return EoBatchLinks{e->Ucb, e->Ucb + (size_t)e->R * V, V, 0.0, e->massv};
+}
+
+// The even-odd action's fields: 32 B per site and replica of checkerboard
+// links, 96 of half-lattice fields and 80 of the batched solver's workspace.
+int eo_fields_ready(sm_ens *e) {
+    if (e->eh) return SM_OK;
+    sm_ctx *c = e->c;
+    const size_t hb = sizeof(double2) * (size_t)c->g.V * (size_t)e->R;
+    int rc = ens_alloc((void **)&e->Ucb, 2 * hb, "checkerboard links");
+    if (rc == SM_OK) rc = eo_batch_ws_alloc(c, e->eows, e->R);
+    if (rc == SM_OK) rc = ens_alloc((void **)&e->eh, EH_N * hb, "even-odd fields");
+    if (rc != SM_OK) {
+        if (e->Ucb) (void)hipFree(e->Ucb);
+        e->Ucb = nullptr;
+        eo_batch_ws_free(e->eows);
+        return rc;
+    }
+    return SM_OK;
+}
+
+// X = (Dhat Dhat^dag)^-1 phi_e of every replica on its current links
+int eo_solve(sm_ens *e, double tol, int max_iter, sm_cg_result *res) {
+    sm_ctx *c = e->c;
+    const EoBatchLinks L = eo_links(e);
+    launch_eob_to_cb(c->stream, c->g, e->R, e->U, e->Ucb, e->Ucb + (size_t)e->R * c->g.V);
+    HIP_TRY(hipGetLastError());
+    return eo_batch_solve(c, e->eows, e->R, eh(e, EH_PHI), eh(e, EH_X), L, tol, max_iter, res);
+}
+
 int upload_params(sm_ens *e) {
     sm_ctx *c = e->c;
     HIP_TRY(hipMemcpyAsync(e->par, e->h_par, sizeof(EnsPar) * (size_t)e->R, hipMemcpyHostToDevice, c->stream));
@@ -111,14 +161,20 @@ int read_sums(sm_ens *e, int nrows) {
 
 // HMC::Hamiltonian + HMC::Action (src/hmc.cpp:104-148) of every replica: rows
 // [0, R) kinetic, [R, 2R) plaquette, [2R, 3R) <x, phi>
-int hamiltonian(sm_ens *e, double tol, int max_iter, std::vector<sm_cg_result> &res, std::vector<HTerms> &h) {
+int hamiltonian(sm_ens *e, bool eo, double tol, int max_iter, std::vector<sm_cg_result> &res,
+                std::vector<HTerms> &h) {
     sm_ctx *c = e->c;
     const int R = e->R;
     const size_t row = (size_t)gauge_reduce_blocks(c->g);
     launch_ens_kinetic(c->stream, c->g, R, e->P, e->part);
     launch_ens_plaquette(c->stream, c->g, R, e->U, e->par, e->part + (size_t)R * row);
     HIP_TRY(hipGetLastError());
-    TRY(cg_batch_solve(c, e->ws, R, e->phi, e->x, links(e), tol, max_iter, res.data()));
+    if (eo) {  // Re <X, phi_e>: e->x = (X, 0) against e->phi = (phi_e, 0)
+        TRY(eo_solve(e, tol, max_iter, res.data()));
+        launch_eob_from_cb(c->stream, c->g, R, eh(e, EH_X), nullptr, e->x);
+    } else {
+        TRY(cg_batch_solve(c, e->ws, R, e->phi, e->x, links(e), tol, max_iter, res.data()));
+    }
     launch_ens_dot(c->stream, c->g, R, e->x, e->phi, e->part + 2 * (size_t)R * row);
     TRY(read_sums(e, 3 * R));
     for (int r = 0; r < R; ++r) {
@@ -242,14 +298,19 @@ int sm_ens_hmc_trajectory(sm_ens *e, const sm_hmc_params *p, uint64_t traj, sm_h
     if (!p || !out) return fail(SM_ERR_ARG, "null argument");
     if (const char *f = sm_ens_host::params_refusal(p, e->R))
         return fail(SM_ERR_ARG,
-                    "ensemble: bad or differing %s (md_steps, cg_tol and cg_max_iter are common to the replicas, tau > 0, "
-                    "even_odd = 0)", f);
+                    "ensemble: bad or differing %s (md_steps, cg_tol, cg_max_iter and even_odd = 0 or 1 are common to "
+                    "the replicas, tau > 0)", f);
     TRY(all_have(e));
     sm_ctx *c = e->c;
+    const bool eo = p[0].even_odd == 1;
+    if (eo && (c->g.Nx % 2 || c->g.Wt % 2))
+        return fail(SM_ERR_ARG, "ensemble: even_odd = 1 needs even Nx and Nt (%d x %d): an odd periodic lattice has no "
+                    "checkerboard", c->g.Nx, c->g.Wt);
     const int R = e->R, md_steps = p[0].md_steps, max_iter = p[0].cg_max_iter;
     const double tol = p[0].cg_tol;
     const Geometry &g = c->g;
     HIP_TRY(hipSetDevice(c->device));
+    if (eo) TRY(eo_fields_ready(e));
     // HMC::HMC_Update, src/hmc.cpp:151-178, for every replica
     for (int r = 0; r < R; ++r) {
         e->h_par[r] = EnsPar{p[r].beta, p[r].tau / (md_steps * 1.0), sm_traj_seed(p[r].seed, traj)};
@@ -258,11 +319,19 @@ int sm_ens_hmc_trajectory(sm_ens *e, const sm_hmc_params *p, uint64_t traj, sm_h
     TRY(upload_params(e));
     const BatchLinks L = links(e);
     launch_ens_draws(c->stream, g, R, e->par, e->P, e->chi);    // RandomPI, RandomCHI
-    launch_batch_apply(c->stream, g, R, 0, e->chi, e->phi, L);  // phi = D chi
+    if (eo) {  // phi = (Dhat chi_e, 0) on the replicas' checkerboard links
+        const EoBatchLinks EL = eo_links(e);
+        launch_eob_to_cb(c->stream, g, R, e->U, e->Ucb, e->Ucb + (size_t)R * g.V);
+        launch_eob_to_cb(c->stream, g, R, e->chi, eh(e, EH_LO), nullptr);
+        launch_eob_dhat(c->stream, g, R, 0, eh(e, EH_LO), eh(e, EH_T), eh(e, EH_PHI), EL);
+        launch_eob_from_cb(c->stream, g, R, eh(e, EH_PHI), nullptr, e->phi);
+    } else {
+        launch_batch_apply(c->stream, g, R, 0, e->chi, e->phi, L);  // phi = D chi
+    }
     HIP_TRY(hipGetLastError());
     std::vector<sm_cg_result> res((size_t)R);
     std::vector<HTerms> h0((size_t)R), h1((size_t)R);
-    TRY(hamiltonian(e, tol, max_iter, res, h0));  // H[U][Pi]
+    TRY(hamiltonian(e, eo, tol, max_iter, res, h0));  // H[U][Pi]
     const size_t fb = sizeof(double2) * slab_complex(e);
     HIP_TRY(hipMemcpyAsync(e->Ubak, e->U, fb * (size_t)R, hipMemcpyDeviceToDevice, c->stream));
     // HMC::Leapfrog, src/hmc.cpp:63-101, its loop bound included: md_steps - 1 forces
@@ -270,8 +339,18 @@ int sm_ens_hmc_trajectory(sm_ens *e, const sm_hmc_params *p, uint64_t traj, sm_h
     std::vector<int> lf_fails((size_t)R, 0);
     double2 *T = e->chi;
     auto force = [&]() -> int {  // HMC::Force, src/hmc.cpp:44-60
-        TRY(cg_batch_solve(c, e->ws, R, e->phi, e->x, L, tol, max_iter, res.data()));
-        launch_batch_apply(c->stream, g, R, 1, e->x, T, L);
+        if (eo) {  // eo_md_force (sm_eo.cpp): l = (X, (1/2m) H'_oe X), r = (Y, (1/2m) H_oe Y), Y = Dhat^dag X
+            TRY(eo_solve(e, tol, max_iter, res.data()));
+            const EoBatchLinks EL = eo_links(e);
+            launch_eob_dhat(c->stream, g, R, 1, eh(e, EH_X), eh(e, EH_T), eh(e, EH_Y), EL);
+            launch_eob_hop(c->stream, g, R, 1, 1, 2, eh(e, EH_X), nullptr, eh(e, EH_LO), EL);
+            launch_eob_hop(c->stream, g, R, 0, 1, 2, eh(e, EH_Y), nullptr, eh(e, EH_RO), EL);
+            launch_eob_from_cb(c->stream, g, R, eh(e, EH_X), eh(e, EH_LO), e->x);
+            launch_eob_from_cb(c->stream, g, R, eh(e, EH_Y), eh(e, EH_RO), T);
+        } else {
+            TRY(cg_batch_solve(c, e->ws, R, e->phi, e->x, L, tol, max_iter, res.data()));
+            launch_batch_apply(c->stream, g, R, 1, e->x, T, L);
+        }
         launch_ens_force(c->stream, g, R, e->U, e->x, T, e->F);
         launch_ens_staple_force(c->stream, g, R, e->U, e->par, e->F);
         HIP_TRY(hipGetLastError());
@@ -289,7 +368,7 @@ int sm_ens_hmc_trajectory(sm_ens *e, const sm_hmc_params *p, uint64_t traj, sm_h
     }
     launch_ens_md_update(c->stream, g, R, e->U, e->P, e->F, e->par, 1, 0.5);
     HIP_TRY(hipGetLastError());
-    TRY(hamiltonian(e, tol, max_iter, res, h1));  // H[U'][Pi']
+    TRY(hamiltonian(e, eo, tol, max_iter, res, h1));  // H[U'][Pi']
     for (int r = 0; r < R; ++r) {
         sm_hmc_result &o = out[r];
         const HTerms &a = h0[(size_t)r], &b = h1[(size_t)r];

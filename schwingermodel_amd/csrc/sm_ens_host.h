@@ -17,10 +17,12 @@ namespace sm_ens_host {
 
 // The first field that keeps p[0..R) from running as one ensemble, or null.
 // Per replica: m0, beta, tau, seed. Common: md_steps, cg_tol, cg_max_iter
-// (the replicas share every launch); even_odd must be 0.
+// (the replicas share every launch), and even_odd, which is 0 (the plain
+// action) or 1 (the even-odd action) for all of them: the two actions run
+// different launches.
 inline const char *params_refusal(const sm_hmc_params *p, int R) {
     for (int r = 0; r < R; ++r) {
-        if (p[r].even_odd != 0) return "even_odd";
+        if ((p[r].even_odd != 0 && p[r].even_odd != 1) || p[r].even_odd != p[0].even_odd) return "even_odd";
         if (p[r].md_steps < 1 || p[r].md_steps != p[0].md_steps) return "md_steps";
         if (p[r].cg_max_iter < 1 || p[r].cg_max_iter != p[0].cg_max_iter) return "cg_max_iter";
         if (!(p[r].cg_tol == p[0].cg_tol)) return "cg_tol";

@@ -413,6 +413,56 @@ void launch_eo_td(hipStream_t s, const Geometry &g, const EoTdCfg &c, const doub
                   int red = 0);  // red: t-shard scalars from sc->sumr (out3 = this pass's sumr slot)
 void launch_pack_cb_faces4(hipStream_t s, const Geometry &g, const double2 *f, double2 *out);
 
+// ---- batched one-pass even-odd CG (sm_eobatch.hip; driver sm_eobatch.cpp) ----
+// K columns on the half lattice, V complex apart (two planes of V/2); one shard.
+// A tile is one wave: kEoTdWaveCols owned k-columns x xchunk rows. Partials per
+// granule of G rows (G from the lattice alone, even), summed in slot order.
+// tiles per launch the tile height aims at: one resident round (256 CUs x 4 SIMDs x 1 wave at the
+// pass's register count)
+constexpr int kEoBatchTargetTiles = 1024;
+struct EoBatchCfg {
+    int NWT;        // wave tiles along k
+    int G, NG;      // rows per granule, granules per column of tiles
+    int P;          // partial slots per column (NWT * NG), 3 complex each
+    int red;        // 1: redundant scalars (P <= kBatchRedMaxSlots)
+    int xchunk;     // rows per tile (a multiple of G)
+    int NCH;        // tiles along x
+    int NB0;        // blocks per column of the start kernel
+    long pstride;   // complex per column in the partials buffer
+};
+EoBatchCfg eo_batch_config(const Geometry &g, int K, int target_tiles = 0);
+// The checkerboard links and mass of each column: column b reads Ue / Uo + b * ustride
+// (complex) and uses massv[b]; ustride = 0 and massv = null: one field and `mass` for all.
+struct EoBatchLinks {
+    const double2 *Ue, *Uo;
+    long ustride;
+    double mass;
+    const double *massv;  // device, K masses (m0 + 2), or null
+};
+// full layout (K x 2V complex) <-> checkerboard (K x V per parity); either parity may be null
+// (from: its sites become 0). Fields and links alike.
+void launch_eob_to_cb(hipStream_t s, const Geometry &g, int K, const double2 *full, double2 *e, double2 *o);
+void launch_eob_from_cb(hipStream_t s, const Geometry &g, int K, const double2 *e, const double2 *o, double2 *full);
+// out_p = hop of in_q on column b's links, scaled with column b's mass m: mode 0: -0.5 H in,
+// 1: m aux + (0.5/m) H in, 2: (0.5/m) H in (launch_eo_hop's arithmetic)
+void launch_eob_hop(hipStream_t s, const Geometry &g, int K, int dagger, int p, int mode, const double2 *in,
+                    const double2 *aux, double2 *out, const EoBatchLinks &l);
+// out = Dhat v (dagger = 0) or Dhat^dag v (1): two hops through the odd work field T
+void launch_eob_dhat(hipStream_t s, const Geometry &g, int K, int dagger, const double2 *v, double2 *T, double2 *out,
+                     const EoBatchLinks &l);
+// x = phi, d0 = r_0 = phi - Dhat Dhat^dag phi (T, W, A: work), and the columns' scalars
+void launch_eo_batch_init(hipStream_t s, const Geometry &g, const EoBatchCfg &c, int K, const double2 *phi, double2 *x,
+                          double2 *T, double2 *W, double2 *A, double2 *d0, const EoBatchLinks &l, double tol,
+                          int max_iter, double2 *partials, CGScalars *sc);
+// pass j of every column that is not done (and, without redundant scalars, its scalar step)
+void launch_eo_batch_pass(hipStream_t s, const Geometry &g, const EoBatchCfg &c, int K, const double2 *d1,
+                          const double2 *d2, const double2 *aold, double2 *dn, double2 *anew, double2 *x,
+                          const EoBatchLinks &l, long pass, CGScalars *sc, double2 *partials);
+void launch_eo_batch_flush(hipStream_t s, const EoBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
+                           long pass);
+void launch_eo_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
+                              const double2 *d1, const double2 *d2, const CGScalars *sc);
+
 // ---- mixed-precision even-odd CG (sm_eosp.hip; driver sm_eomp.cpp) ----
 // Pass `pass` of a segment on float2 checkerboard fields (0: the injected
 // direction, no d store; even passes >= 2 update y): d_{j-1} in d1, d_{j-2} in

@@ -19,6 +19,16 @@ the sequential median by more than that spread. --seq-cap C (0: off) runs only
 the first C chains of the sequential side when R > C and scales their time by
 R / C; such rows say so ("seq_chains_run").
 
+--even-odd times the even-odd ensemble (even_odd = 1 for every replica)
+instead, against two baselines on identical parameters, seeds and start fields:
+the plain-action ensemble (the path without this option), and -- with
+--eo-seq -- the same chains one after another through
+sm_hmc_trajectory(even_odd = 1) (--seq-cap applies). Pairs are interleaved and
+medians reported as above; a row gives the time against the plain ensemble, CG
+iterations per trajectory and replica for both, and "pays" only where the
+even-odd median beats the plain one by more than the plain side's spread.
+Output: profiles/hmc_ensemble_eo_<build id>.json.
+
 --stats N,R runs the reference protocol (Ntherm 50, Nmeas 100, Nsteps 1) on an
 ensemble and reports the mean of the replicas' Ep with its error from their
 scatter next to the manifest's pooled reference value, and the pull.
@@ -44,8 +54,8 @@ def vp(a):
     return ctypes.c_void_p(a.ctypes.data)
 
 
-def params(sm, R):
-    return [sm.HMCParams(M0, BETA, TAU, MD_STEPS, TOL, MAXIT, 1 + r, 0) for r in range(R)]
+def params(sm, R, even_odd=0):
+    return [sm.HMCParams(M0, BETA, TAU, MD_STEPS, TOL, MAXIT, 1 + r, even_odd) for r in range(R)]
 
 
 def hot_fields(sm, N, R):
@@ -115,6 +125,58 @@ def measure(sm, N, R, ntraj, warmup, pairs, seq_cap):
     }
 
 
+def measure_eo(sm, N, R, ntraj, warmup, pairs, seq_cap, with_seq):
+    """The even-odd ensemble against the plain-action ensemble (and, with_seq,
+    lone even-odd chains one after another) from the same hot fields."""
+    L = sm.Lattice(N, N)
+    pe, pp = params(sm, R, 1), params(sm, R, 0)
+    fields = hot_fields(sm, N, R)
+    Ee, Ep = L.ensemble(R), L.ensemble(R)
+    for r in range(R):
+        Ee.upload_gauge(r, fields[r])
+        Ep.upload_gauge(r, fields[r])
+    nseq = 0 if not with_seq else (R if not seq_cap or R <= seq_cap else seq_cap)
+    ens_window(Ee, pe, 0, warmup)
+    ens_window(Ep, pp, 0, warmup)
+    for r in range(nseq):
+        lone_window(sm, L, pe[r], fields[r], 0, warmup)
+    eo_s, pl_s, seq_s, eo_it, pl_it, seq_it = [], [], [], 0, 0, 0
+    for i in range(pairs):
+        first = warmup + i * ntraj
+        dt, it = ens_window(Ee, pe, first, ntraj)
+        eo_s.append(dt)
+        eo_it += it
+        dt, it = ens_window(Ep, pp, first, ntraj)
+        pl_s.append(dt)
+        pl_it += it
+        tot = 0.0
+        for r in range(nseq):
+            dt, it = lone_window(sm, L, pe[r], fields[r], first, ntraj)
+            tot += dt
+            seq_it += it
+        if nseq:
+            seq_s.append(tot * R / nseq)
+    Ee.close()
+    Ep.close()
+    L.close()
+    em, pm = statistics.median(eo_s), statistics.median(pl_s)
+    spread = (max(pl_s) - min(pl_s)) / pm
+    n = pairs * ntraj * R
+    row = {
+        "N": N, "R": R, "trajectories": ntraj, "pairs": pairs, "eo_s": eo_s, "plain_s": pl_s,
+        "eo_median_s": em, "plain_median_s": pm, "plain_spread": spread, "speedup_vs_plain": pm / em,
+        "pays": bool(em < pm * (1.0 - spread)),
+        "eo_ms_per_traj_replica": 1e3 * em / (ntraj * R), "plain_ms_per_traj_replica": 1e3 * pm / (ntraj * R),
+        "cg_iterations_per_traj_replica": {"eo": eo_it / n, "plain": pl_it / n},
+        "seq_chains_run": nseq,
+    }
+    if nseq:
+        sq = statistics.median(seq_s)
+        row.update({"seq_eo_s": seq_s, "seq_eo_median_s": sq, "speedup_vs_seq_eo": sq / em})
+        row["cg_iterations_per_traj_replica"]["seq_eo"] = seq_it / (pairs * ntraj * nseq)
+    return row
+
+
 def stats_run(sm, N, R):
     with open(os.path.join(REPO, "tests", "golden", "manifest.json")) as f:
         m = json.load(f)
@@ -151,6 +213,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--pairs", type=int, default=3)
     ap.add_argument("--seq-cap", type=int, default=0)
+    ap.add_argument("--even-odd", action="store_true")
+    ap.add_argument("--eo-seq", action="store_true")
     ap.add_argument("--stats", default=None, metavar="N,R")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
@@ -167,6 +231,14 @@ def main():
 
     for N in [int(x) for x in a.lattices.split(",") if x]:
         for R in [int(x) for x in a.R.split(",") if x]:
+            if a.even_odd:
+                row = measure_eo(sm, N, R, a.traj, a.warmup, a.pairs, a.seq_cap, a.eo_seq)
+                result["rows"].append(row)
+                print(json.dumps({k: row.get(k) for k in ("N", "R", "eo_median_s", "plain_median_s", "plain_spread",
+                                                          "speedup_vs_plain", "pays", "speedup_vs_seq_eo",
+                                                          "cg_iterations_per_traj_replica")}), flush=True)
+                dump()
+                continue
             row = measure(sm, N, R, a.traj, a.warmup, a.pairs, a.seq_cap)
             result["rows"].append(row)
             print(json.dumps({k: row[k] for k in ("N", "R", "ens_median_s", "seq_median_s", "seq_spread", "speedup",

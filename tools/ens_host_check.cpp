@@ -70,6 +70,21 @@ static void check_params() {
     refused(1, [](sm_hmc_params &x) { x.cg_tol = std::nan(""); }, "cg_tol");
     refused(1, [](sm_hmc_params &x) { x.cg_max_iter = 99; }, "cg_max_iter");
     refused(2, [](sm_hmc_params &x) { x.even_odd = 1; }, "even_odd");
+    refused(0, [](sm_hmc_params &x) { x.even_odd = 1; }, "even_odd");   // replica 0 alone differs
+    refused(1, [](sm_hmc_params &x) { x.even_odd = 2; }, "even_odd");
+    refused(1, [](sm_hmc_params &x) { x.even_odd = -1; }, "even_odd");
+    {  // even_odd is a lockstep parameter: 1 for every replica passes, 2 for every replica does not
+        std::vector<sm_hmc_params> q = p;
+        for (sm_hmc_params &x : q) x.even_odd = 1;
+        CHECK(params_refusal(q.data(), 3) == nullptr);
+        q[1].md_steps = 7;  // and the other checks still apply to it
+        const char *f = params_refusal(q.data(), 3);
+        CHECK(f && std::string(f) == "md_steps");
+        q = p;
+        for (sm_hmc_params &x : q) x.even_odd = 2;
+        f = params_refusal(q.data(), 3);
+        CHECK(f && std::string(f) == "even_odd");
+    }
     refused(1, [](sm_hmc_params &x) { x.tau = 0.0; }, "tau");
     refused(1, [](sm_hmc_params &x) { x.tau = std::nan(""); }, "tau");
 }
