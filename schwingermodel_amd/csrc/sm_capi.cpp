@@ -43,6 +43,18 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
+void free_dev(void *p) {
+    if (p) (void)hipFree(p);
+}
+
+int alloc_dev(void **p, size_t bytes, const char *who, const char *what) {
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) return SM_OK;
+    *p = nullptr;
+    (void)hipGetLastError();
+    return fail(SM_ERR_HIP, "%s: allocating %zu bytes (%s) failed: %s", who, bytes, what, hipGetErrorString(e));
+}
+
 // Neighbour sources for `in`: periodic aliases (1 GPU) or received faces.
 TFaces faces_for(sm_ctx *c, const double2 *in, const double2 *recv_lo, const double2 *recv_hi) {
     TFaces f;

@@ -2,7 +2,8 @@
 // and of every HIP header so that tools/mixed_driver_check.cpp and
 // tools/batch_mixed_driver_check.cpp can run it under the host sanitizers: the
 // chunk planner of every CG host, the chunked status loop of the fp64
-// one-column ones, and the reliable-update driver of the three mixed-precision
+// one-column ones (cg_chunked) and of every K-column host
+// (cg_chunked_columns), and the reliable-update driver of the three mixed-precision
 // solvers (sm_cgmp.cpp, sm_eomp.cpp, sm_cgbatchmp.cpp), which is described
 // here and nowhere else: one loop on K columns, and MixedColumn, which hands it
 // a one-column solver's operations as K = 1.
@@ -100,6 +101,41 @@ int cg_chunked(long limit, Issue issue, Status status, bool *done = nullptr) {
     return SM_OK;
 }
 
+// The same loop on K columns that stop one by one, the only copy: the fp64
+// batched hosts (sm_ctx.h batch_cg_solve) and cg_mixed_drive's rounds run it.
+// Up to `limit` passes in chunks that start at 4: issue(j, nb) enqueues passes
+// j .. j + nb - 1, read(issued) is the caller's read-back of all K states with
+// whatever it launches before it, status(b) column b's CgStatus (done: it is
+// over, or not part of this loop). One CgChunker per column; of the columns
+// still running the longest wish wins, 2 at the least. debug(issued, running,
+// wish) is the caller's line after each read. Stops when no column runs or at
+// the limit; *ended (nullable) says whether every column was seen done. With
+// K = 1 the chunks are cg_chunked's.
+template <class Issue, class Read, class Status, class Debug>
+int cg_chunked_columns(int K, long limit, Issue issue, Read read, Status status, Debug debug, bool *ended = nullptr) {
+    std::vector<CgChunker> plan((size_t)K);
+    int chunk = CgChunker().chunk, running = 1;
+    for (long issued = 0; issued < limit && running;) {
+        const long nb = limit - issued < chunk ? limit - issued : chunk;
+        TRY(issue(issued, nb));
+        issued += nb;
+        TRY(read(issued));
+        running = 0;
+        int wish = 2;
+        for (int b = 0; b < K; ++b) {
+            const CgStatus st = status(b);
+            if (st.done) continue;
+            ++running;
+            const int w = plan[(size_t)b].next(st.k, st.err, st.target);
+            if (w > wish) wish = w;
+        }
+        debug(issued, running, wish);
+        chunk = wish;
+    }
+    if (ended) *ended = !running;
+    return SM_OK;
+}
+
 // The reliable-update driver of the mixed-precision solvers, on operator A
 // (D D^dag or Dhat Dhat^dag) and K <= 64 columns, each a solve of its own:
 //
@@ -119,9 +155,9 @@ int cg_chunked(long limit, Issue issue, Status status, bool *done = nullptr) {
 // to the fp64 solver: A e = r with its own x0 = r convention, x += e.
 //
 // The columns go in rounds: inject for the open columns, passes in chunks until
-// every open column's segment has ended (one CgChunker per column, the longest
-// wish wins, all K scalar blocks read once per chunk: with K = 1 the sequence
-// of cg_chunked), fold, one true residual for the open columns, then the
+// every open column's segment has ended (cg_chunked_columns, all K scalar
+// blocks read once per chunk: with K = 1 the sequence of cg_chunked), fold,
+// one true residual for the open columns, then the
 // decisions column by column. A column whose segment ended early idles until
 // the round is over; a column that has stopped, or is marked for the fp64
 // finish, is closed: nothing of it is touched again before the finishes, which
@@ -185,27 +221,22 @@ int cg_mixed_drive(Ops &o, int K, sm_cg_result *res) {
         long limit = 0;  // every column stops itself at its own max_iter
         for (int b = 0; b < K; ++b)
             if ((open & bit(b)) && (long)(max_iter - o.h(b).k_total) + 1 > limit) limit = (long)(max_iter - o.h(b).k_total) + 1;
-        std::vector<CgChunker> plan((size_t)K);
-        long j = 0;
-        int chunk = plan[0].chunk;
         bool ended = false;
-        while (j < limit && !ended) {
-            const long nb = limit - j < chunk ? limit - j : chunk;
-            for (long i = 0; i < nb; ++i, ++j) o.pass(j, open);
-            TRY(o.read());
-            ended = true;
-            int wish = 2, running = 0;
-            for (int b = 0; b < K; ++b) {
+        TRY(cg_chunked_columns(
+            K, limit,
+            [&](long j, long nb) {
+                for (long i = 0; i < nb; ++i) o.pass(j + i, open);
+                return SM_OK;
+            },
+            [&](long) { return o.read(); },
+            [&](int b) {
                 const sm::MPScalars &h = o.h(b);
-                if (!(open & bit(b)) || h.done) continue;
-                ended = false;
-                ++running;
-                const int w = plan[(size_t)b].next(h.k, h.err, std::fmax(o.delta * h.M, tol * h.phi_norm));
-                if (w > wish) wish = w;
-            }
-            if (o.debug) fprintf(stderr, "[%s]   passes %ld running %d next chunk %d\n", o.tag, j, running, wish);
-            chunk = wish;
-        }
+                return CgStatus{h.k, h.err, std::fmax(o.delta * h.M, tol * h.phi_norm), !(open & bit(b)) || h.done};
+            },
+            [&](long j, int running, int wish) {
+                if (o.debug) fprintf(stderr, "[%s]   passes %ld running %d next chunk %d\n", o.tag, j, running, wish);
+            },
+            &ended));
         if (!ended) return fail(SM_ERR_STATE, "%s", o.stuck);
         ColMask bad = 0;
         for (int b = 0; b < K; ++b) {

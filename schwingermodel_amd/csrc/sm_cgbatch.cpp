@@ -5,10 +5,12 @@
 //   start   x_b = phi_b, r_0 = phi_b - D D^dag phi_b, d_0 = r_0, the column's
 //           scalars (3 launches for the whole batch)
 //   pass j  the stored-Ad two-direction iteration of every column that is not
-//           done, column b with its own alpha, beta, stop test and partials;
-//           passes are enqueued in chunks (CgChunker per column, the longest
-//           wish wins) and all K states are read once per chunk
+//           done, column b with its own alpha, beta, stop test and partials
 //   finish  x_b += alpha_{k-1} d_{k-1} where column b's iteration count is odd
+// The host of these steps is sm_ctx.h's batch_cg_solve, which the even-odd
+// solver (sm_eobatch.cpp) runs too: cg_batch_solve below hands it this
+// operator's two launchers. The workspace of both solvers (batch_ws_alloc,
+// batch_ws_free) is defined here.
 //
 // One-shard contexts only. fp64 unless sm_cg_batch_precision switched the entry
 // points below to the mixed-precision solver (sm_cgbatchmp.cpp), which shares
@@ -31,11 +33,7 @@ using namespace sm;
 
 namespace sm_host {
 
-static void free_dev(void *p) {
-    if (p) (void)hipFree(p);
-}
-
-void cg_batch_ws_free(CGBatchWs &w) {
+void batch_ws_free(BatchWs &w) {
     for (double2 *&d : w.d) {
         free_dev(d);
         d = nullptr;
@@ -50,10 +48,11 @@ void cg_batch_ws_free(CGBatchWs &w) {
     w.partials = nullptr;
     w.sc = w.h_sc = nullptr;
     w.K = 0;
+    w.n = 0;
 }
 
 void cg_batch_free(sm_ctx *c) {
-    cg_batch_ws_free(c->bt);
+    batch_ws_free(c->bt);
     free_dev(c->bt_phi);
     free_dev(c->bt_x);
     free_dev(c->bt_src);
@@ -64,37 +63,26 @@ void cg_batch_free(sm_ctx *c) {
     c->bt_pion_K = 0;
 }
 
-// hipMalloc that reports the request on failure and leaves no sticky error
-static int alloc_dev(void **p, size_t bytes, const char *what) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return SM_OK;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(SM_ERR_HIP, "batched CG: allocating %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
-}
-
-// The solver's workspace for K columns: three d buffers, two Ad buffers
-// (K x 32 V bytes each), partials and scalars.
-int cg_batch_ws_alloc(sm_ctx *c, CGBatchWs &w, int K) {
+// Three d buffers, two Ad buffers (K x 16 n bytes each), partials and scalars.
+int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride, const char *who) {
     HIP_TRY(hipStreamSynchronize(c->stream));
-    cg_batch_ws_free(w);
-    const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
-    const CGBatchCfg cfg = cg_batch_config(c->g, K, c->bt_tiles);  // pstride does not depend on K
-    const size_t pb = sizeof(double2) * (size_t)cfg.pstride * (size_t)K;
+    batch_ws_free(w);
+    const size_t fb = sizeof(double2) * (size_t)n * (size_t)K;
+    const size_t pb = sizeof(double2) * (size_t)pstride * (size_t)K;
     int rc = SM_OK;
     for (double2 *&d : w.d)
-        if (rc == SM_OK) rc = alloc_dev((void **)&d, fb, "direction buffer");
+        if (rc == SM_OK) rc = alloc_dev((void **)&d, fb, who, "direction buffer");
     for (double2 *&a : w.a)
-        if (rc == SM_OK) rc = alloc_dev((void **)&a, fb, "Ad buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, "partials");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sizeof(CGScalars) * (size_t)K, "scalars");
+        if (rc == SM_OK) rc = alloc_dev((void **)&a, fb, who, "Ad buffer");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, who, "partials");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sizeof(CGScalars) * (size_t)K, who, "scalars");
     if (rc == SM_OK && hipHostMalloc((void **)&w.h_sc, sizeof(CGScalars) * (size_t)K) != hipSuccess) {
         w.h_sc = nullptr;
         (void)hipGetLastError();
-        rc = fail(SM_ERR_HIP, "batched CG: allocating %zu pinned bytes (scalars) failed", sizeof(CGScalars) * (size_t)K);
+        rc = fail(SM_ERR_HIP, "%s: allocating %zu pinned bytes (scalars) failed", who, sizeof(CGScalars) * (size_t)K);
     }
     if (rc != SM_OK) {
-        cg_batch_ws_free(w);
+        batch_ws_free(w);
         return rc;
     }
     // every buffer is read by halo lanes / rows before its first write: defined values
@@ -103,13 +91,15 @@ int cg_batch_ws_alloc(sm_ctx *c, CGBatchWs &w, int K) {
     HIP_TRY(hipMemsetAsync(w.partials, 0, pb, c->stream));
     HIP_TRY(hipMemsetAsync(w.sc, 0, sizeof(CGScalars) * (size_t)K, c->stream));
     w.K = K;
+    w.n = n;
     return SM_OK;
 }
 
 // The context's own workspace: kept while K fits, regrown else.
 static int batch_ready(sm_ctx *c, int K) {
     HIP_TRY(hipSetDevice(c->device));
-    return c->bt.K >= K ? SM_OK : cg_batch_ws_alloc(c, c->bt, K);
+    if (c->bt.K >= K) return SM_OK;
+    return batch_ws_alloc(c, c->bt, K, 2 * c->g.V, cg_batch_config(c->g, K, c->bt_tiles).pstride, kBatchWho);
 }
 
 // Device staging for the host-pointer entry and the correlator: phi and x, K columns.
@@ -121,8 +111,8 @@ static int staging_ready(sm_ctx *c, int K) {
     c->bt_phi = c->bt_x = nullptr;
     c->bt_pion_K = 0;
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
-    int rc = alloc_dev((void **)&c->bt_phi, fb, "sources");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->bt_x, fb, "solutions");
+    int rc = alloc_dev((void **)&c->bt_phi, fb, kBatchWho, "sources");
+    if (rc == SM_OK) rc = alloc_dev((void **)&c->bt_x, fb, kBatchWho, "solutions");
     if (rc != SM_OK) {
         free_dev(c->bt_phi);
         c->bt_phi = nullptr;
@@ -140,51 +130,17 @@ static int batch_check(sm_ctx *c, int K) {
     return SM_OK;
 }
 
-int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
+int cg_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res) {
-    HIP_TRY(hipSetDevice(c->device));
-    const CGBatchCfg cfg = cg_batch_config(c->g, K, c->bt_tiles);
-    auto dbuf = [&](long i) { return w.d[((i % 3) + 3) % 3]; };
-    // d_0 goes where pass 0 expects d_{-1}: it copies it to dbuf(0) while forming Ad_0
-    launch_cg_batch_init(c->stream, c->g, cfg, K, phi, x, w.a[0], dbuf(-1), l, tol, max_iter, w.partials, w.sc);
-    HIP_TRY(hipGetLastError());
-    const long passes = (long)max_iter + 1;  // pass 0 forms Ad_0; a column stops itself at k == max_iter
-    std::vector<CgChunker> plan((size_t)K);
-    long issued = 0;
-    int chunk = 4;
-    const CGScalars *h = w.h_sc;
-    for (;;) {
-        const long nb = passes - issued < chunk ? passes - issued : chunk;
-        for (long i = 0; i < nb; ++i, ++issued) {
-            const long j = issued;
-            launch_cg_batch_pass(c->stream, c->g, cfg, K, dbuf(j - 1), dbuf(j - 2), w.a[(j + 1) & 1], dbuf(j),
-                                 w.a[j & 1], x, l, j, w.sc, w.partials);
-        }
-        if (nb > 0) launch_cg_batch_flush(c->stream, cfg, K, w.partials, w.sc, issued - 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(w.h_sc, w.sc, sizeof(CGScalars) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        int open = 0, wish = 2;
-        for (int b = 0; b < K; ++b) {
-            if (h[b].done) continue;
-            ++open;
-            const int w = plan[(size_t)b].next(h[b].k, h[b].err, tol * h[b].phi_norm);
-            if (w > wish) wish = w;
-        }
-        if (c->debug_cg) fprintf(stderr, "[sm cg batch] passes %ld open %d of %d next chunk %d\n", issued, open, K, wish);
-        if (!open || issued >= passes) break;
-        chunk = wish;
-    }
-    launch_cg_batch_finish_x(c->stream, c->g, K, x, w.d[0], w.d[1], w.d[2], w.sc);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < K; ++b) {
-        res[b].converged = h[b].converged;
-        res[b].iterations = h[b].k;
-        res[b].residual = h[b].err;
-        res[b].phi_norm = h[b].phi_norm;
-    }
-    return SM_OK;
+    const BatchCfg cfg = cg_batch_config(c->g, K, c->bt_tiles);
+    return batch_cg_solve(
+        c, w, cfg, K, x, tol, max_iter, res, "sm cg batch",
+        [&](auto dbuf) {  // d_0 goes where pass 0 expects d_{-1}: it copies it to dbuf(0) while forming Ad_0
+            launch_cg_batch_init(c->stream, c->g, cfg, K, phi, x, w.a[0], dbuf(-1), l, tol, max_iter, w.partials, w.sc);
+        },
+        [&](long j, const double2 *d1, const double2 *d2, const double2 *aold, double2 *dn, double2 *anew) {
+            launch_cg_batch_pass(c->stream, c->g, cfg, K, d1, d2, aold, dn, anew, x, l, j, w.sc, w.partials);
+        });
 }
 
 // Every batched solve of the entry points below: this file's fp64 solver on the
@@ -247,8 +203,9 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
     TRY(check_ready(c));
     HIP_TRY(hipSetDevice(c->device));
     TRY(staging_ready(c, K));
-    if (!c->bt_src) TRY(alloc_dev((void **)&c->bt_src, sizeof(int) * kBatchMax, "source coordinates"));
-    if (!c->bt_C) TRY(alloc_dev((void **)&c->bt_C, sizeof(double) * (kBatchMax / 2) * (size_t)c->g.Wt, "correlator"));
+    if (!c->bt_src) TRY(alloc_dev((void **)&c->bt_src, sizeof(int) * kBatchMax, kBatchWho, "source coordinates"));
+    if (!c->bt_C) TRY(alloc_dev((void **)&c->bt_C, sizeof(double) * (kBatchMax / 2) * (size_t)c->g.Wt, kBatchWho,
+                                   "correlator"));
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
     int *sx = c->bt_src, *st = c->bt_src + kBatchMax / 2;
     // pageable host memory: the copies have left the caller's arrays when they return

@@ -44,6 +44,16 @@
 // L2 round trip ahead of the march instead of two. Larger P: a scalar kernel of
 // K blocks after each pass. A finished column's tiles return at entry, its
 // fields, scalars and partials are never touched again.
+//
+// Everything of this scheme outside the pass kernel -- the slot-order sum, the
+// scalar kernel, the flush for the host, the start's scalars and finish-x, with
+// BatchCfg and its arithmetic (batch_config) -- is written for a column of n
+// complex and P slots, not for this operator: the even-odd solver
+// (sm_eobatch.hip) launches the same kernels through launch_batch_scalars,
+// launch_batch_flush, launch_batch_init_scalars and launch_batch_finish_x, and
+// both pass launchers end in sm_device.h's launch_batch_pass. A column's bits
+// depend on the slot-order sum and on cg1_eval / cg1_update; there is one copy
+// of each.
 #include "sm_device.h"
 #include "sm_internal.h"
 
@@ -272,8 +282,8 @@ __device__ __forceinline__ void batch_sum3(int P, const double2 *part, double2 *
 }
 
 // Scalar step of the non-redundant path: block b evaluates column b.
-__global__ void __launch_bounds__(256) cg_batch_scalar_kernel(int P, const double2 *partials, long pstride,
-                                                              CGScalars *sc, int first) {
+__global__ void __launch_bounds__(256) batch_scalar_kernel(int P, const double2 *partials, long pstride, CGScalars *sc,
+                                                           int first) {
     __shared__ double2 sh[4];
     sc += blockIdx.x;
     if (sc->done) return;
@@ -284,8 +294,8 @@ __global__ void __launch_bounds__(256) cg_batch_scalar_kernel(int P, const doubl
 
 // Redundant path: S_J of the last issued pass J for the host, one wave per
 // column, summed as the pass's tiles sum (the next pass recomputes the same S_J).
-__global__ void __launch_bounds__(64) cg_batch_flush_kernel(int P, const double2 *partials, long pstride,
-                                                            CGScalars *sc, long J) {
+__global__ void __launch_bounds__(64) batch_flush_kernel(int P, const double2 *partials, long pstride, CGScalars *sc,
+                                                         long J) {
     sc += blockIdx.x;
     const double2 *prev = partials + blockIdx.x * pstride;
     const double2 zz = make_double2(0.0, 0.0);
@@ -404,9 +414,9 @@ __global__ void __launch_bounds__(256) batch_init_scalars_kernel(int NB0, const 
     }
 }
 
-// After the last pass: a column whose iteration count k is odd still lacks
-// alpha_{k-1} d_{k-1} in x (cg_td_finish_x_kernel's rule, per column).
-__global__ void __launch_bounds__(256) batch_finish_x_kernel(int NBF, long V, double2 *x, const double2 *d0,
+// After the last pass: a column (n complex) whose iteration count k is odd still
+// lacks alpha_{k-1} d_{k-1} in x (cg_td_finish_x_kernel's rule, per column).
+__global__ void __launch_bounds__(256) batch_finish_x_kernel(int NBF, long n, double2 *x, const double2 *d0,
                                                              const double2 *d1, const double2 *d2,
                                                              const CGScalars *sc) {
     const int b = blockIdx.x / NBF, q = blockIdx.x - b * NBF;
@@ -415,30 +425,33 @@ __global__ void __launch_bounds__(256) batch_finish_x_kernel(int NBF, long V, do
     if (k < 1 || !(k & 1)) return;
     const double2 alpha = sc->done ? sc->alpha : sc->alpha2;
     const int i3 = (k - 1) % 3;
-    const long col = (long)b * 2 * V;
+    const long col = (long)b * n;
     const double2 *d = (i3 == 0 ? d0 : (i3 == 1 ? d1 : d2)) + col;
-    for (long i = (long)q * 256 + threadIdx.x; i < 2 * V; i += (long)NBF * 256)
+    for (long i = (long)q * 256 + threadIdx.x; i < n; i += (long)NBF * 256)
         x[col + i] = cadd(x[col + i], cmul(alpha, d[i]));
 }
 
-CGBatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles) {
-    CGBatchCfg c;
-    c.NWT = (g.Wt + BW - 1) / BW;
-    c.G = g.Nx >= 512 ? 8 : 1;
+BatchCfg batch_config(const Geometry &g, int K, int width, int extent, int small_G, int target_tiles) {
+    BatchCfg c;
+    c.NWT = (extent + width - 1) / width;
+    c.G = g.Nx >= 512 ? 8 : small_G;
     c.NG = (g.Nx + c.G - 1) / c.G;
     c.P = c.NWT * c.NG;
     c.red = c.P <= kBatchRedMaxSlots ? 1 : 0;
-    if (target_tiles < 1) target_tiles = kBatchTargetTiles;
     long nch = target_tiles / ((long)K * c.NWT);
     if (nch > c.NG) nch = c.NG;
     if (nch < 1) nch = 1;
     const int m = (int)((c.NG + nch - 1) / nch);  // granules per tile
     c.xchunk = m * c.G;
     c.NCH = (g.Nx + c.xchunk - 1) / c.xchunk;
-    c.NB0 = (int)((g.V + 255) / 256 < 1024 ? (g.V + 255) / 256 : 1024);
-    const long need = 6L * c.P > 2L * c.NB0 ? 6L * c.P : 2L * c.NB0;  // partials by pass parity / the start's
-    c.pstride = need;
+    const long nb = (g.V + 255) / 256;
+    c.NB0 = (int)(nb < 1024 ? nb : 1024);
+    c.pstride = 6L * c.P > 2L * c.NB0 ? 6L * c.P : 2L * c.NB0;  // partials by pass parity / the start's
     return c;
+}
+
+BatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles) {
+    return batch_config(g, K, BW, g.Wt, 1, target_tiles < 1 ? kBatchTargetTiles : target_tiles);
 }
 
 void launch_batch_apply(hipStream_t s, const Geometry &g, int K, int dagger, const double2 *in, double2 *out,
@@ -448,57 +461,50 @@ void launch_batch_apply(hipStream_t s, const Geometry &g, int K, int dagger, con
     else hipLaunchKernelGGL(batch_apply_kernel<0>, grid, dim3(256), 0, s, g.Nx, g.Wt, g.V, in, l, out);
 }
 
-void launch_cg_batch_init(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *phi, double2 *x,
+void launch_cg_batch_init(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *phi, double2 *x,
                           double2 *T, double2 *d0, const BatchLinks &l, double tol, int max_iter, double2 *partials,
                           CGScalars *sc) {
     launch_batch_apply(s, g, K, 1, phi, T, l);
     hipLaunchKernelGGL(batch_init_kernel, dim3(K * c.NB0), dim3(256), 0, s, c.NB0, g.Nx, g.Wt, g.V, phi, T, l, x, d0,
                        partials, c.pstride);
-    hipLaunchKernelGGL(batch_init_scalars_kernel, dim3(K), dim3(256), 0, s, c.NB0, partials, c.pstride, sc, tol,
-                       max_iter);
+    launch_batch_init_scalars(s, c, K, partials, sc, tol, max_iter);
 }
 
-void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *dold,
+void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *dold,
                           const double2 *rold, const double2 *aold, double2 *dnew, double2 *anew, double2 *x,
                           const BatchLinks &l, long pass, CGScalars *sc, double2 *partials) {
     CGBArgs a;
     a.dold = dold; a.rold = rold; a.aold = aold;
     a.dnew = dnew; a.anew = anew;
     a.x = x; a.U = l.U; a.ustride = l.ustride; a.massv = l.massv;
-    a.sc = sc;
-    a.pstride = c.pstride;
-    // redundant scalars: partials by pass parity, 3 P apart
-    a.partials = partials + (c.red ? (pass & 1) * 3L * c.P : 0);
-    a.prev = partials + ((pass + 1) & 1) * 3L * c.P;
-    a.pass = pass;
     a.V = g.V; a.Nx = g.Nx; a.Wt = g.Wt;
-    a.xchunk = c.xchunk; a.G = c.G; a.NG = c.NG; a.NWT = c.NWT; a.NCH = c.NCH; a.P = c.P;
     a.mass = l.mass;
-    const dim3 grid((unsigned)(K * c.NWT * c.NCH)), block(64);
-    const bool xp = pass >= 2 && (pass & 1) == 0;
-    if (c.red) {
-        if (xp) hipLaunchKernelGGL((cg_batch_kernel<1, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((cg_batch_kernel<1, 0>), grid, block, 0, s, a);
-    } else {
-        if (xp) hipLaunchKernelGGL((cg_batch_kernel<0, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((cg_batch_kernel<0, 0>), grid, block, 0, s, a);
-        hipLaunchKernelGGL(cg_batch_scalar_kernel, dim3(K), dim3(256), 0, s, c.P, partials, c.pstride, sc,
-                           pass == 0 ? 1 : 0);
-    }
+    void (*const kern[2][2])(CGBArgs) = {{cg_batch_kernel<0, 0>, cg_batch_kernel<0, 1>},
+                                         {cg_batch_kernel<1, 0>, cg_batch_kernel<1, 1>}};
+    launch_batch_pass(s, c, K, pass, sc, partials, a, kern);
 }
 
-void launch_cg_batch_flush(hipStream_t s, const CGBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
-                           long pass) {
+void launch_batch_scalars(hipStream_t s, const BatchCfg &c, int K, const double2 *partials, CGScalars *sc, long pass) {
+    hipLaunchKernelGGL(batch_scalar_kernel, dim3(K), dim3(256), 0, s, c.P, partials, c.pstride, sc, pass == 0 ? 1 : 0);
+}
+
+void launch_batch_flush(hipStream_t s, const BatchCfg &c, int K, const double2 *partials, CGScalars *sc, long pass) {
     if (!c.red) return;  // the scalar kernel has already evaluated the pass
-    hipLaunchKernelGGL(cg_batch_flush_kernel, dim3(K), dim3(64), 0, s, c.P, partials + (pass & 1) * 3L * c.P,
-                       c.pstride, sc, pass);
+    hipLaunchKernelGGL(batch_flush_kernel, dim3(K), dim3(64), 0, s, c.P, partials + (pass & 1) * 3L * c.P, c.pstride,
+                       sc, pass);
 }
 
-void launch_cg_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
-                              const double2 *d1, const double2 *d2, const CGScalars *sc) {
-    const long nb = (2 * g.V + 255) / 256;
+void launch_batch_init_scalars(hipStream_t s, const BatchCfg &c, int K, const double2 *partials, CGScalars *sc,
+                               double tol, int max_iter) {
+    hipLaunchKernelGGL(batch_init_scalars_kernel, dim3(K), dim3(256), 0, s, c.NB0, partials, c.pstride, sc, tol,
+                       max_iter);
+}
+
+void launch_batch_finish_x(hipStream_t s, int K, long n, double2 *x, const double2 *d0, const double2 *d1,
+                           const double2 *d2, const CGScalars *sc) {
+    const long nb = (n + 255) / 256;
     const int NBF = (int)(nb < 256 ? nb : 256);
-    hipLaunchKernelGGL(batch_finish_x_kernel, dim3(K * NBF), dim3(256), 0, s, NBF, g.V, x, d0, d1, d2, sc);
+    hipLaunchKernelGGL(batch_finish_x_kernel, dim3(K * NBF), dim3(256), 0, s, NBF, n, x, d0, d1, d2, sc);
 }
 
 // ---- pion correlator -------------------------------------------------------

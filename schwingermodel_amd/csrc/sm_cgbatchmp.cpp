@@ -35,17 +35,10 @@ void cg_batch_mixed_free(sm_ctx *c) {
     w = CGBatchMixedWs{};
 }
 
-// hipMalloc that reports the request on failure and leaves no sticky error
-static int alloc_dev(void **p, size_t bytes, const char *what) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return SM_OK;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(SM_ERR_HIP, "mixed batched CG: allocating %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(e));
-}
+constexpr const char *kWho = "mixed batched CG";  // the error prefix
 
 static size_t partials_per_column(const sm_ctx *c) {
-    const CGBatchCfg cfg = cg_batch_config(c->g, 1, c->bt_tiles);  // P does not depend on K
+    const BatchCfg cfg = cg_batch_config(c->g, 1, c->bt_tiles);  // P does not depend on K
     const size_t nbr = (size_t)batch_mp_blocks(c->g);
     return 2 * (size_t)cfg.P > nbr ? 2 * (size_t)cfg.P : nbr;
 }
@@ -60,20 +53,20 @@ static int mixed_ready(sm_ctx *c, int K) {
     const size_t pb = sizeof(double2) * partials_per_column(c) * (size_t)K, sb = sizeof(MPScalars) * (size_t)K;
     int rc = SM_OK;
     for (float2 *&d : w.d)
-        if (rc == SM_OK) rc = alloc_dev((void **)&d, f32, "direction buffer");
+        if (rc == SM_OK) rc = alloc_dev((void **)&d, f32, kWho, "direction buffer");
     for (float2 *&a : w.a)
-        if (rc == SM_OK) rc = alloc_dev((void **)&a, f32, "Ad buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.y, f32, "correction");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.U, sizeof(float2) * n, "links");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.r, f64, "residual");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.t, f64, "D^dag x");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.ax, f64, "D D^dag x");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, "partials");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sb, "scalars");
+        if (rc == SM_OK) rc = alloc_dev((void **)&a, f32, kWho, "Ad buffer");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.y, f32, kWho, "correction");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.U, sizeof(float2) * n, kWho, "links");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.r, f64, kWho, "residual");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.t, f64, kWho, "D^dag x");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.ax, f64, kWho, "D D^dag x");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, kWho, "partials");
+    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sb, kWho, "scalars");
     if (rc == SM_OK && hipHostMalloc((void **)&w.h_sc, sb) != hipSuccess) {
         w.h_sc = nullptr;
         (void)hipGetLastError();
-        rc = fail(SM_ERR_HIP, "mixed batched CG: allocating %zu pinned bytes (scalars) failed", sb);
+        rc = fail(SM_ERR_HIP, "%s: allocating %zu pinned bytes (scalars) failed", kWho, sb);
     }
     if (rc != SM_OK) {
         cg_batch_mixed_free(c);
@@ -98,7 +91,7 @@ struct BatchOps {
     double2 *x;
     double m0, tol;
     int max_iter;
-    CGBatchCfg cfg;
+    BatchCfg cfg;
     const char *tag = "sm cg batch mixed";
     const char *stuck = "mixed-precision batched CG: a segment did not end at max_iter";
     double delta = c->mp_delta;
@@ -140,7 +133,8 @@ struct BatchOps {
     void fold(ColMask m, ColMask discard) { launch_batch_mp_fold(c->stream, c->g, K, m, discard, x, w.y, w.d, w.sc); }
     // A e = r_b through the fp64 batched solver with K = 1 (its own x0 = r convention), x_b += e
     int finish(int b, double tol64, int iters, sm_cg_result *r64) {
-        if (c->bt.K < 1) TRY(cg_batch_ws_alloc(c, c->bt, 1));
+        if (c->bt.K < 1)
+            TRY(batch_ws_alloc(c, c->bt, 1, n, cg_batch_config(c->g, 1, c->bt_tiles).pstride, kBatchWho));
         double2 *e = w.t + b * n;
         TRY(cg_batch_solve(c, c->bt, 1, w.r + b * n, e, links, tol64, iters, r64));
         launch_mp_add(c->stream, n, x + b * n, e);

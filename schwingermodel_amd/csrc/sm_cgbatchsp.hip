@@ -322,7 +322,7 @@ int batch_mp_blocks(const Geometry &g) {
     return (int)(nb < 256 ? nb : 256);
 }
 
-void launch_cg_batch_sp(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, unsigned long long mask,
+void launch_cg_batch_sp(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, unsigned long long mask,
                         float2 *const d[3], float2 *const ad[2], float2 *y, const float2 *U32, double mass, long pass,
                         MPScalars *sc, double2 *partials) {
     auto dbuf = [&](long i) { return d[((i % 3) + 3) % 3]; };

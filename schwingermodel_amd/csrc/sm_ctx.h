@@ -9,6 +9,7 @@
 
 #include <cmath>
 #include <cstddef>
+#include <cstdio>
 #include <vector>
 
 #include "sm_internal.h"
@@ -40,24 +41,16 @@ namespace sm_host {  // fail, TRY: sm_cg_host.h (through sm_internal.h)
 // six-launch path); F_AD2: the second Ad buffer of the stored-Ad pass (ping-pong with F_AD).
 enum { F_IN, F_OUT, F_TMP, F_X, F_R, F_D, F_D2, F_T, F_AD, F_PHI, F_L, F_RR, F_AD2, NFIELDS };
 
-// Workspace of a batched CG solve of up to K columns (sm_cgbatch.cpp): the
-// context owns one for sm_cg_batch, a replica ensemble (sm_ens.cpp) its own.
-struct CGBatchWs {
+// Workspace of an fp64 batched CG solve of up to K columns of n complex, the
+// full-lattice solver's (sm_cgbatch.cpp, n = 2V) or the even-odd one's
+// (sm_eobatch.cpp, n = V): the context owns one of each for sm_cg_batch and
+// sm_eo_cg_batch, a replica ensemble (sm_ens.cpp) its own.
+struct BatchWs {
     int K = 0;                      // columns it holds
-    double2 *d[3] = {};             // d_i in d[i mod 3], K x 2V complex each
+    long n = 0;                     // complex per column
+    double2 *d[3] = {};             // d_i in d[i mod 3], K x n complex each
     double2 *a[2] = {};             // Ad by pass parity
-    double2 *partials = nullptr;    // K x CGBatchCfg::pstride
-    sm::CGScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
-};
-
-// Workspace of a batched even-odd CG solve of up to K columns (sm_eobatch.cpp),
-// half-lattice vectors of V complex per column: the context owns one for
-// sm_eo_cg_batch, a replica ensemble its own.
-struct EoBatchWs {
-    int K = 0;                      // columns it holds
-    double2 *d[3] = {};             // d_i in d[i mod 3], K x V complex each
-    double2 *a[2] = {};             // Ad by pass parity
-    double2 *partials = nullptr;    // K x EoBatchCfg::pstride
+    double2 *partials = nullptr;    // K x BatchCfg::pstride
     sm::CGScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
 };
 
@@ -257,7 +250,7 @@ struct sm_ctx {
     // Ad buffers, scalars and partials for bt.K columns, from the first batched
     // solve on and regrown for a larger K. Reads c->U at every call; keeps
     // nothing that depends on the gauge field.
-    CGBatchWs bt;                   // the solver's workspace
+    BatchWs bt;                     // the solver's workspace
     int bt_tiles = 0;               // test option batch_tiles=N: tiles per launch aimed at (0: kBatchTargetTiles)
     // sm_cg_batch(_dev) and the correlator's solve run fp32 inner iterations with
     // fp64 reliable updates when bt_precision == 1 (sm_cgbatchmp.cpp). Independent
@@ -277,7 +270,7 @@ struct sm_ctx {
     // columns' even parts (eob_K columns) and the host-pointer entry's
     // full-layout staging (eob_fK columns), all from the first call on. Shares
     // nothing with eo / Ucb, the mixed solvers, bt or the stepwise solver.
-    EoBatchWs eob;
+    BatchWs eob;
     int eob_tiles = 0;              // test option eo_batch_tiles=N: tiles per launch aimed at (0: kEoBatchTargetTiles)
     double2 *eob_U = nullptr;       // even links, then odd links: 2V complex
     int eob_K = 0, eob_fK = 0;
@@ -405,29 +398,74 @@ struct MixedDev {
         return SM_OK;
     }
 };
-void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's workspaces (sm_cgbatch.cpp)
-// A batched solve's workspace for K columns on c's lattice (zeroed; SM_ERR_HIP
-// names the bytes on failure and leaves w empty), and the solve itself on any
-// such workspace: K columns of phi -> x, column b on l's links and mass.
-int cg_batch_ws_alloc(sm_ctx *c, CGBatchWs &w, int K);
-void cg_batch_ws_free(CGBatchWs &w);
-int cg_batch_solve(sm_ctx *c, const CGBatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
+// hipFree of a pointer that may be null; hipMalloc that reports the request as
+// "<who>: allocating ... (<what>) failed" and leaves no sticky error (sm_capi.cpp)
+void free_dev(void *p);
+int alloc_dev(void **p, size_t bytes, const char *who, const char *what);
+
+// ---- the fp64 batched CG hosts (sm_cgbatch.cpp, sm_eobatch.cpp) ----
+constexpr const char *kBatchWho = "batched CG", *kEoBatchWho = "batched even-odd CG";  // their error prefixes
+// A workspace for K columns of n complex with pstride complex of partials per
+// column (the solver's BatchCfg::pstride, which does not depend on K), zeroed;
+// SM_ERR_HIP names the bytes under `who` on failure and leaves w empty.
+int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride, const char *who);
+void batch_ws_free(BatchWs &w);
+// The host of both solvers, the only copy: init(dbuf) starts the columns (x =
+// phi, d_0 where pass 0 expects d_{-1}, the scalars), then up to max_iter + 1
+// passes (pass 0 forms Ad_0; a column stops itself at k == max_iter) through
+// cg_chunked_columns (sm_cg_host.h), pass(j, d_{j-1}, d_{j-2}, Ad_{j-1}, d_j,
+// Ad_j) being the operator's launcher; after each chunk the flush and one read
+// of all K scalar blocks; then finish-x and the results. tag: of the debug line.
+template <class Init, class Pass>
+int batch_cg_solve(sm_ctx *c, const BatchWs &w, const BatchCfg &cfg, int K, double2 *x, double tol, int max_iter,
+                   sm_cg_result *res, const char *tag, Init init, Pass pass) {
+    HIP_TRY(hipSetDevice(c->device));
+    auto dbuf = [&](long i) { return w.d[((i % 3) + 3) % 3]; };
+    init(dbuf);
+    HIP_TRY(hipGetLastError());
+    const CGScalars *h = w.h_sc;
+    TRY(cg_chunked_columns(
+        K, (long)max_iter + 1,
+        [&](long j0, long nb) {
+            for (long j = j0; j < j0 + nb; ++j) pass(j, dbuf(j - 1), dbuf(j - 2), w.a[(j + 1) & 1], dbuf(j), w.a[j & 1]);
+            return SM_OK;
+        },
+        [&](long issued) {
+            launch_batch_flush(c->stream, cfg, K, w.partials, w.sc, issued - 1);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(w.h_sc, w.sc, sizeof(CGScalars) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(hipStreamSynchronize(c->stream));
+            return SM_OK;
+        },
+        [&](int b) { return CgStatus{h[b].k, h[b].err, tol * h[b].phi_norm, h[b].done}; },
+        [&](long issued, int open, int wish) {
+            if (c->debug_cg) fprintf(stderr, "[%s] passes %ld open %d of %d next chunk %d\n", tag, issued, open, K, wish);
+        }));
+    launch_batch_finish_x(c->stream, K, w.n, x, w.d[0], w.d[1], w.d[2], w.sc);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < K; ++b) {
+        res[b].converged = h[b].converged;
+        res[b].iterations = h[b].k;
+        res[b].residual = h[b].err;
+        res[b].phi_norm = h[b].phi_norm;
+    }
+    return SM_OK;
+}
+// The two entry points on any such workspace: K columns of phi -> x, column b
+// on l's links and mass (even-odd: even vectors, V complex apart, on l's
+// checkerboard links); and what frees the context's workspaces and staging.
+int cg_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res);
+int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
+                   double tol, int max_iter, sm_cg_result *res);
+void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's (sm_cgbatch.cpp)
+void eo_batch_free(sm_ctx *c);
 // The mixed-precision batched solve on the context's gauge field (sm_cgbatchmp.cpp):
 // K columns of phi -> x on the device, c->bt_info[b] = column b's report.
 int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
                    sm_cg_result *res);
 void cg_batch_mixed_free(sm_ctx *c);
-
-// The batched even-odd CG (sm_eobatch.cpp): a workspace for K columns on c's
-// lattice (zeroed; SM_ERR_HIP names the bytes on failure and leaves w empty),
-// and the solve on any such workspace: K even vectors phi -> x (V complex
-// apart), column b on l's checkerboard links and mass.
-void eo_batch_free(sm_ctx *c);
-int eo_batch_ws_alloc(sm_ctx *c, EoBatchWs &w, int K);
-void eo_batch_ws_free(EoBatchWs &w);
-int eo_batch_solve(sm_ctx *c, const EoBatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
-                   double tol, int max_iter, sm_cg_result *res);
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

@@ -646,5 +646,25 @@ __device__ __forceinline__ void cg_ticketed_tail(double2 *partials, long tile, i
     }
 }
 
+// What the pass launchers of the two fp64 batched solvers (sm_cgbatch.hip,
+// sm_eobatch.hip) share. `a` holds the operator's fields, links and lattice
+// already; this adds the tiles, the scalars and the partials of pass `pass`
+// (redundant scalars: by pass parity, 3 P apart, `prev` = pass - 1's), launches
+// kern[red][xp] on K x NWT x NCH tiles of one wave (xp: x takes two updates,
+// even passes from 2 on) and, without redundant scalars, the scalar step.
+template <class Args>
+void launch_batch_pass(hipStream_t s, const BatchCfg &c, int K, long pass, CGScalars *sc, double2 *partials, Args &a,
+                       void (*const kern[2][2])(Args)) {
+    a.sc = sc;
+    a.pstride = c.pstride;
+    a.partials = partials + (c.red ? (pass & 1) * 3L * c.P : 0);
+    a.prev = partials + ((pass + 1) & 1) * 3L * c.P;
+    a.pass = pass;
+    a.xchunk = c.xchunk; a.G = c.G; a.NG = c.NG; a.NWT = c.NWT; a.NCH = c.NCH; a.P = c.P;
+    const bool xp = pass >= 2 && (pass & 1) == 0;
+    hipLaunchKernelGGL(kern[c.red][xp], dim3((unsigned)(K * c.NWT * c.NCH)), dim3(64), 0, s, a);
+    if (!c.red) launch_batch_scalars(s, c, K, partials, sc, pass);
+}
+
 }  // namespace sm
 

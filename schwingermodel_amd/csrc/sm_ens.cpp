@@ -47,14 +47,14 @@ struct sm_ens {
     double2 *U = nullptr, *Ubak = nullptr;                  // R x 2V complex
     double2 *chi = nullptr, *phi = nullptr, *x = nullptr;   // chi doubles as T = D^dag psi of the force
     double *P = nullptr, *F = nullptr;                      // R x 2V doubles
-    CGBatchWs ws;
+    BatchWs ws;
     EnsPar *par = nullptr, *h_par = nullptr;                // device, pinned host
     double *massv = nullptr, *h_mass = nullptr;             // m0 + 2 per replica
     double2 *part = nullptr;                                // 3 x R x gauge_reduce_blocks partials
     double2 *sums = nullptr, *h_sums = nullptr;             // 3 x R
     std::vector<char> have;                                 // replica r holds a gauge field
     // even-odd action, from the first even-odd trajectory on
-    EoBatchWs eows;
+    BatchWs eows;
     double2 *Ucb = nullptr;                                 // even links R x V complex, then odd links R x V
     double2 *eh = nullptr;                                  // EH_N half-lattice fields, R x V complex each
 };
@@ -81,8 +81,8 @@ void ens_free(sm_ens *e) {
     void *host[] = {e->h_par, e->h_mass, e->h_sums};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
-    cg_batch_ws_free(e->ws);
-    eo_batch_ws_free(e->eows);
+    batch_ws_free(e->ws);
+    batch_ws_free(e->eows);
     delete e;
 }
 
@@ -122,12 +122,13 @@ int eo_fields_ready(sm_ens *e) {
     sm_ctx *c = e->c;
     const size_t hb = sizeof(double2) * (size_t)c->g.V * (size_t)e->R;
     int rc = ens_alloc((void **)&e->Ucb, 2 * hb, "checkerboard links");
-    if (rc == SM_OK) rc = eo_batch_ws_alloc(c, e->eows, e->R);
+    if (rc == SM_OK)
+        rc = batch_ws_alloc(c, e->eows, e->R, c->g.V, eo_batch_config(c->g, e->R, c->eob_tiles).pstride, kEoBatchWho);
     if (rc == SM_OK) rc = ens_alloc((void **)&e->eh, EH_N * hb, "even-odd fields");
     if (rc != SM_OK) {
         if (e->Ucb) (void)hipFree(e->Ucb);
         e->Ucb = nullptr;
-        eo_batch_ws_free(e->eows);
+        batch_ws_free(e->eows);
         return rc;
     }
     return SM_OK;
@@ -223,7 +224,8 @@ int sm_ens_create(sm_ctx *c, int R, sm_ens **out) {
     if (rc == SM_OK) rc = ens_alloc((void **)&e->h_par, sizeof(EnsPar) * (size_t)R, "pinned parameters", true);
     if (rc == SM_OK) rc = ens_alloc((void **)&e->h_mass, sizeof(double) * (size_t)R, "pinned masses", true);
     if (rc == SM_OK) rc = ens_alloc((void **)&e->h_sums, sizeof(double2) * nsum, "pinned sums", true);
-    if (rc == SM_OK) rc = cg_batch_ws_alloc(c, e->ws, R);
+    if (rc == SM_OK)
+        rc = batch_ws_alloc(c, e->ws, R, 2 * c->g.V, cg_batch_config(c->g, R, c->bt_tiles).pstride, kBatchWho);
     if (rc != SM_OK) {
         ens_free(e);
         return rc;

@@ -5,14 +5,15 @@
 //   start   x_b = phi_b, r_0 = phi_b - Dhat Dhat^dag phi_b, d_0 = r_0, the
 //           column's scalars (6 launches for the whole batch)
 //   pass j  sm_eotd.hip's iteration of every column that is not done, column b
-//           with its own links, mass, alpha, beta, stop test and partials;
-//           passes are enqueued in chunks (CgChunker per column, the longest
-//           wish wins) and all K states are read once per chunk
+//           with its own links, mass, alpha, beta, stop test and partials
 //   finish  x_b += alpha_{k-1} d_{k-1} where column b's iteration count is odd
+// The host of these steps is sm_ctx.h's batch_cg_solve, shared with
+// sm_cgbatch.cpp; eo_batch_solve below hands it this operator's two launchers.
 //
 // One-shard contexts, always fp64: none of the precision switches reaches it.
-// The workspace (three direction and two Ad buffers on the half lattice,
-// partials, scalars) is its own and is allocated at first use; the entry
+// The workspace (a BatchWs of V complex per column: three direction and two Ad
+// buffers on the half lattice, partials, scalars; batch_ws_alloc in
+// sm_cgbatch.cpp) is its own and is allocated at first use; the entry
 // points add the checkerboard copy of c->U and the columns' even parts. Nothing
 // is shared with the context's even-odd solver (c->eo, c->Ucb), the mixed
 // solvers, sm_cg_batch or the stepwise solver. The checkerboard links are
@@ -21,9 +22,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <vector>
-
 #include "sm_ctx.h"
 #include "sm_internal.h"
 
@@ -31,29 +29,8 @@ using namespace sm;
 
 namespace sm_host {
 
-static void free_dev(void *p) {
-    if (p) (void)hipFree(p);
-}
-
-void eo_batch_ws_free(EoBatchWs &w) {
-    for (double2 *&d : w.d) {
-        free_dev(d);
-        d = nullptr;
-    }
-    for (double2 *&a : w.a) {
-        free_dev(a);
-        a = nullptr;
-    }
-    free_dev(w.partials);
-    free_dev(w.sc);
-    if (w.h_sc) (void)hipHostFree(w.h_sc);
-    w.partials = nullptr;
-    w.sc = w.h_sc = nullptr;
-    w.K = 0;
-}
-
 void eo_batch_free(sm_ctx *c) {
-    eo_batch_ws_free(c->eob);
+    batch_ws_free(c->eob);
     free_dev(c->eob_U);
     free_dev(c->eob_phi);
     free_dev(c->eob_x);
@@ -63,104 +40,26 @@ void eo_batch_free(sm_ctx *c) {
     c->eob_K = c->eob_fK = 0;
 }
 
-// hipMalloc that reports the request on failure and leaves no sticky error
-static int alloc_dev(void **p, size_t bytes, const char *what) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return SM_OK;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(SM_ERR_HIP, "batched even-odd CG: allocating %zu bytes (%s) failed: %s", bytes, what,
-                hipGetErrorString(e));
-}
-
-// The solver's workspace for K columns: three d buffers, two Ad buffers
-// (K x 16 V bytes each), partials and scalars.
-int eo_batch_ws_alloc(sm_ctx *c, EoBatchWs &w, int K) {
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    eo_batch_ws_free(w);
-    const size_t fb = sizeof(double2) * (size_t)c->g.V * (size_t)K;
-    const EoBatchCfg cfg = eo_batch_config(c->g, K, c->eob_tiles);  // pstride does not depend on K
-    const size_t pb = sizeof(double2) * (size_t)cfg.pstride * (size_t)K;
-    int rc = SM_OK;
-    for (double2 *&d : w.d)
-        if (rc == SM_OK) rc = alloc_dev((void **)&d, fb, "direction buffer");
-    for (double2 *&a : w.a)
-        if (rc == SM_OK) rc = alloc_dev((void **)&a, fb, "Ad buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, "partials");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sizeof(CGScalars) * (size_t)K, "scalars");
-    if (rc == SM_OK && hipHostMalloc((void **)&w.h_sc, sizeof(CGScalars) * (size_t)K) != hipSuccess) {
-        w.h_sc = nullptr;
-        (void)hipGetLastError();
-        rc = fail(SM_ERR_HIP, "batched even-odd CG: allocating %zu pinned bytes (scalars) failed",
-                  sizeof(CGScalars) * (size_t)K);
-    }
-    if (rc != SM_OK) {
-        eo_batch_ws_free(w);
-        return rc;
-    }
-    // every buffer is read by halo lanes / rows before its first write: defined values
-    for (double2 *d : w.d) HIP_TRY(hipMemsetAsync(d, 0, fb, c->stream));
-    for (double2 *a : w.a) HIP_TRY(hipMemsetAsync(a, 0, fb, c->stream));
-    HIP_TRY(hipMemsetAsync(w.partials, 0, pb, c->stream));
-    HIP_TRY(hipMemsetAsync(w.sc, 0, sizeof(CGScalars) * (size_t)K, c->stream));
-    w.K = K;
-    return SM_OK;
-}
-
-int eo_batch_solve(sm_ctx *c, const EoBatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
+int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res) {
-    HIP_TRY(hipSetDevice(c->device));
-    const EoBatchCfg cfg = eo_batch_config(c->g, K, c->eob_tiles);
-    auto dbuf = [&](long i) { return w.d[((i % 3) + 3) % 3]; };
-    // the start's work fields are free until pass 0 writes them; d_0 goes where pass 0 expects d_{-1}
-    launch_eo_batch_init(c->stream, c->g, cfg, K, phi, x, w.a[0], w.a[1], dbuf(0), dbuf(-1), l, tol, max_iter,
-                         w.partials, w.sc);
-    HIP_TRY(hipGetLastError());
-    const long passes = (long)max_iter + 1;  // pass 0 forms Ad_0; a column stops itself at k == max_iter
-    std::vector<CgChunker> plan((size_t)K);
-    long issued = 0;
-    int chunk = 4;
-    const CGScalars *h = w.h_sc;
-    for (;;) {
-        const long nb = passes - issued < chunk ? passes - issued : chunk;
-        for (long i = 0; i < nb; ++i, ++issued) {
-            const long j = issued;
-            launch_eo_batch_pass(c->stream, c->g, cfg, K, dbuf(j - 1), dbuf(j - 2), w.a[(j + 1) & 1], dbuf(j),
-                                 w.a[j & 1], x, l, j, w.sc, w.partials);
-        }
-        if (nb > 0) launch_eo_batch_flush(c->stream, cfg, K, w.partials, w.sc, issued - 1);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(w.h_sc, w.sc, sizeof(CGScalars) * (size_t)K, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        int open = 0, wish = 2;
-        for (int b = 0; b < K; ++b) {
-            if (h[b].done) continue;
-            ++open;
-            const int wb = plan[(size_t)b].next(h[b].k, h[b].err, tol * h[b].phi_norm);
-            if (wb > wish) wish = wb;
-        }
-        if (c->debug_cg)
-            fprintf(stderr, "[sm eo cg batch] passes %ld open %d of %d next chunk %d\n", issued, open, K, wish);
-        if (!open || issued >= passes) break;
-        chunk = wish;
-    }
-    launch_eo_batch_finish_x(c->stream, c->g, K, x, w.d[0], w.d[1], w.d[2], w.sc);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < K; ++b) {
-        res[b].converged = h[b].converged;
-        res[b].iterations = h[b].k;
-        res[b].residual = h[b].err;
-        res[b].phi_norm = h[b].phi_norm;
-    }
-    return SM_OK;
+    const BatchCfg cfg = eo_batch_config(c->g, K, c->eob_tiles);
+    return batch_cg_solve(
+        c, w, cfg, K, x, tol, max_iter, res, "sm eo cg batch",
+        [&](auto dbuf) {  // the start's work fields are free until pass 0 writes them; d_0 goes where pass 0 expects d_{-1}
+            launch_eo_batch_init(c->stream, c->g, cfg, K, phi, x, w.a[0], w.a[1], dbuf(0), dbuf(-1), l, tol, max_iter,
+                                 w.partials, w.sc);
+        },
+        [&](long j, const double2 *d1, const double2 *d2, const double2 *aold, double2 *dn, double2 *anew) {
+            launch_eo_batch_pass(c->stream, c->g, cfg, K, d1, d2, aold, dn, anew, x, l, j, w.sc, w.partials);
+        });
 }
 
 // The context's own workspace and half-lattice staging: kept while K fits, regrown else.
 static int eob_ready(sm_ctx *c, int K) {
     HIP_TRY(hipSetDevice(c->device));
-    if (c->eob.K < K) TRY(eo_batch_ws_alloc(c, c->eob, K));
-    if (!c->eob_U) TRY(alloc_dev((void **)&c->eob_U, sizeof(double2) * 2 * (size_t)c->g.V, "checkerboard links"));
+    if (c->eob.K < K)
+        TRY(batch_ws_alloc(c, c->eob, K, c->g.V, eo_batch_config(c->g, K, c->eob_tiles).pstride, kEoBatchWho));
+    if (!c->eob_U) TRY(alloc_dev((void **)&c->eob_U, sizeof(double2) * 2 * (size_t)c->g.V, kEoBatchWho, "checkerboard links"));
     if (c->eob_K >= K) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_dev(c->eob_phi);
@@ -168,8 +67,8 @@ static int eob_ready(sm_ctx *c, int K) {
     c->eob_phi = c->eob_x = nullptr;
     c->eob_K = 0;
     const size_t hb = sizeof(double2) * (size_t)c->g.V * (size_t)K;
-    int rc = alloc_dev((void **)&c->eob_phi, hb, "even sources");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->eob_x, hb, "even solutions");
+    int rc = alloc_dev((void **)&c->eob_phi, hb, kEoBatchWho, "even sources");
+    if (rc == SM_OK) rc = alloc_dev((void **)&c->eob_x, hb, kEoBatchWho, "even solutions");
     if (rc != SM_OK) {
         free_dev(c->eob_phi);
         c->eob_phi = nullptr;
@@ -188,8 +87,8 @@ static int eob_staging_ready(sm_ctx *c, int K) {
     c->eob_fphi = c->eob_fx = nullptr;
     c->eob_fK = 0;
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
-    int rc = alloc_dev((void **)&c->eob_fphi, fb, "sources");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->eob_fx, fb, "solutions");
+    int rc = alloc_dev((void **)&c->eob_fphi, fb, kEoBatchWho, "sources");
+    if (rc == SM_OK) rc = alloc_dev((void **)&c->eob_fx, fb, kEoBatchWho, "solutions");
     if (rc != SM_OK) {
         free_dev(c->eob_fphi);
         c->eob_fphi = nullptr;

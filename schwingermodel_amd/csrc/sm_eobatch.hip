@@ -29,10 +29,12 @@
 // its value: a column's bits do not depend on K, its position, the other
 // columns or the tile height.
 //
-// Scalars: P <= kBatchRedMaxSlots: every tile of pass j sums its own column's
-// partials of pass j-1 (kept by pass parity) and evaluates S_{j-1} itself; the
-// column's first tile stores it. Larger P: one scalar kernel of K blocks after
-// the pass. No floating-point atomics anywhere.
+// Scalars: sm_cgbatch.hip's scheme and its kernels (its header has both):
+// redundant scalars in the pass up to kBatchRedMaxSlots slots, the scalar
+// kernel above; the flush, the start's scalars and finish-x are launched from
+// there too (launch_batch_*), on columns of V complex. This file keeps the
+// operator: the pass, the hops, the start's residual and the layout kernels.
+// No floating-point atomics anywhere.
 #include <type_traits>
 
 #include "sm_device.h"
@@ -343,57 +345,6 @@ __global__ void __launch_bounds__(64) eo_batch_kernel(EOBArgs a) {
     }
 }
 
-// A column's three sums in slot order by one block of 256 threads.
-__device__ __forceinline__ void eob_sum3(int P, const double2 *part, double2 *sh, double2 t[3]) {
-    const double2 zz = make_double2(0.0, 0.0);
-    double2 acc[3] = {zz, zz, zz};
-    for (int i = threadIdx.x; i < P; i += blockDim.x) {
-        acc[0] = cadd(acc[0], part[3 * (long)i]);
-        acc[1] = cadd(acc[1], part[3 * (long)i + 1]);
-        acc[2] = cadd(acc[2], part[3 * (long)i + 2]);
-    }
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-        t[q] = block_sum(acc[q], sh);
-        __syncthreads();
-    }
-}
-
-// Scalar step of the non-redundant path: block b evaluates column b.
-__global__ void __launch_bounds__(256) eo_batch_scalar_kernel(int P, const double2 *partials, long pstride,
-                                                              CGScalars *sc, int first) {
-    __shared__ double2 sh[4];
-    sc += blockIdx.x;
-    if (sc->done) return;
-    double2 t[3];
-    eob_sum3(P, partials + blockIdx.x * pstride, sh, t);
-    if (threadIdx.x == 0) cg1_update(sc, first, t[0], t[1], t[2]);
-}
-
-// Redundant path: S_J of the last issued pass J for the host, one wave per
-// column, summed as the pass's tiles sum (the next pass recomputes the same S_J).
-__global__ void __launch_bounds__(64) eo_batch_flush_kernel(int P, const double2 *partials, long pstride,
-                                                            CGScalars *sc, long J) {
-    sc += blockIdx.x;
-    const double2 *prev = partials + blockIdx.x * pstride;
-    const double2 zz = make_double2(0.0, 0.0);
-    double2 acc0 = zz, acc1 = zz, acc2 = zz;
-    for (int i = threadIdx.x; i < P; i += 64) {
-        acc0 = cadd(acc0, prev[3 * i]);
-        acc1 = cadd(acc1, prev[3 * i + 1]);
-        acc2 = cadd(acc2, prev[3 * i + 2]);
-    }
-    CGRed s = sc->red[(J + 1) & 1];  // S_{J-1}
-    if (!s.done) {
-        const double2 t0 = wave_sum(acc0), t1 = wave_sum(acc1), t2 = wave_sum(acc2);
-        s = cg1_eval(s, sc->tol, sc->phi_norm, sc->max_iter, J == 0, t0, t1, t2);
-    }
-    if (threadIdx.x == 0) {
-        sc->red[J & 1] = s;
-        store_state(sc, s);
-    }
-}
-
 // ---- layout: full <-> checkerboard, column / replica b = blockIdx.y ----------
 // (to_cb_kernel's / from_cb_kernel's site map, sm_eo.hip; either parity may be null)
 __global__ void __launch_bounds__(256) eob_to_cb_kernel(int Wt, long V, const double2 *full, double2 *e, double2 *o) {
@@ -493,77 +444,10 @@ __global__ void __launch_bounds__(256) eob_init_kernel(int NB0, long n2, const d
     }
 }
 
-__global__ void __launch_bounds__(256) eob_init_scalars_kernel(int NB0, const double2 *partials, long pstride,
-                                                               CGScalars *sc, double tol, int max_iter) {
-    __shared__ double2 sh[4];
-    sc += blockIdx.x;
-    const double2 *p = partials + blockIdx.x * pstride;
-    double2 arr = make_double2(0.0, 0.0), app = make_double2(0.0, 0.0);
-    for (int i = threadIdx.x; i < NB0; i += 256) {
-        arr = cadd(arr, p[2 * i]);
-        app = cadd(app, p[2 * i + 1]);
-    }
-    const double2 rr = block_sum(arr, sh);
-    __syncthreads();
-    const double2 pp = block_sum(app, sh);
-    if (threadIdx.x == 0) {
-        const double2 zz = make_double2(0.0, 0.0);
-        sc->rn = rr;
-        sc->phi_norm = sqrt(pp.x);
-        sc->tol = tol;
-        sc->err = 0.0;
-        sc->k = 0;
-        sc->done = 0;
-        sc->converged = 0;
-        sc->max_iter = max_iter;
-        sc->alpha = sc->beta = sc->alpha2 = sc->beta2 = sc->sum = zz;
-        CGRed s0;  // S_-1
-        s0.rn = rr;
-        s0.alpha = s0.beta = s0.alpha2 = s0.beta2 = zz;
-        s0.err = 0.0;
-        s0.k = s0.done = s0.converged = s0.pad = 0;
-        sc->red[0] = s0;
-        sc->red[1] = s0;
-    }
-}
-
-// After the last pass: a column whose iteration count k is odd still lacks alpha_{k-1} d_{k-1} in x.
-__global__ void __launch_bounds__(256) eob_finish_x_kernel(int NBF, long n2, double2 *x, const double2 *d0,
-                                                           const double2 *d1, const double2 *d2,
-                                                           const CGScalars *sc) {
-    const int b = blockIdx.x / NBF, q = blockIdx.x - b * NBF;
-    sc += b;
-    const int k = sc->k;
-    if (k < 1 || !(k & 1)) return;
-    const double2 alpha = sc->done ? sc->alpha : sc->alpha2;
-    const int i3 = (k - 1) % 3;
-    const long col = (long)b * n2;
-    const double2 *d = (i3 == 0 ? d0 : (i3 == 1 ? d1 : d2)) + col;
-    for (long i = (long)q * 256 + threadIdx.x; i < n2; i += (long)NBF * 256)
-        x[col + i] = cadd(x[col + i], cmul(alpha, d[i]));
-}
-
 }  // namespace
 
-EoBatchCfg eo_batch_config(const Geometry &g, int K, int target_tiles) {
-    EoBatchCfg c;
-    const int Wh = g.Wt / 2;
-    c.NWT = (Wh + QW - 1) / QW;
-    c.G = g.Nx >= 512 ? 8 : 2;
-    c.NG = (g.Nx + c.G - 1) / c.G;
-    c.P = c.NWT * c.NG;
-    c.red = c.P <= kBatchRedMaxSlots ? 1 : 0;
-    if (target_tiles < 1) target_tiles = kEoBatchTargetTiles;
-    long nch = target_tiles / ((long)K * c.NWT);
-    if (nch > c.NG) nch = c.NG;
-    if (nch < 1) nch = 1;
-    const int mg = (int)((c.NG + nch - 1) / nch);  // granules per tile
-    c.xchunk = mg * c.G;
-    c.NCH = (g.Nx + c.xchunk - 1) / c.xchunk;
-    const long nb = (g.V + 255) / 256;  // the column's V complex entries
-    c.NB0 = (int)(nb < 1024 ? nb : 1024);
-    c.pstride = 6L * c.P > 2L * c.NB0 ? 6L * c.P : 2L * c.NB0;  // partials by pass parity / the start's
-    return c;
+BatchCfg eo_batch_config(const Geometry &g, int K, int target_tiles) {
+    return batch_config(g, K, QW, g.Wt / 2, 2, target_tiles < 1 ? kEoBatchTargetTiles : target_tiles);
 }
 
 void launch_eob_to_cb(hipStream_t s, const Geometry &g, int K, const double2 *full, double2 *e, double2 *o) {
@@ -591,55 +475,26 @@ void launch_eob_dhat(hipStream_t s, const Geometry &g, int K, int dagger, const 
     launch_eob_hop(s, g, K, dagger, 0, 1, T, v, out, l);      // m v + (0.5/m) H_eo T
 }
 
-void launch_eo_batch_init(hipStream_t s, const Geometry &g, const EoBatchCfg &c, int K, const double2 *phi, double2 *x,
+void launch_eo_batch_init(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *phi, double2 *x,
                           double2 *T, double2 *W, double2 *A, double2 *d0, const EoBatchLinks &l, double tol,
                           int max_iter, double2 *partials, CGScalars *sc) {
     launch_eob_dhat(s, g, K, 1, phi, T, W, l);
     launch_eob_dhat(s, g, K, 0, W, T, A, l);
     hipLaunchKernelGGL(eob_init_kernel, dim3(K * c.NB0), dim3(256), 0, s, c.NB0, g.V, phi, A, x, d0, partials,
                        c.pstride);
-    hipLaunchKernelGGL(eob_init_scalars_kernel, dim3(K), dim3(256), 0, s, c.NB0, partials, c.pstride, sc, tol,
-                       max_iter);
+    launch_batch_init_scalars(s, c, K, partials, sc, tol, max_iter);
 }
 
-void launch_eo_batch_pass(hipStream_t s, const Geometry &g, const EoBatchCfg &c, int K, const double2 *d1,
+void launch_eo_batch_pass(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *d1,
                           const double2 *d2, const double2 *aold, double2 *dn, double2 *anew, double2 *x,
                           const EoBatchLinks &l, long pass, CGScalars *sc, double2 *partials) {
     EOBArgs a;
     a.d1 = d1; a.d2 = d2; a.aold = aold; a.dn = dn; a.anew = anew; a.x = x;
     a.Ue = l.Ue; a.Uo = l.Uo; a.ustride = l.ustride; a.massv = l.massv; a.mass = l.mass;
-    a.sc = sc;
-    a.pstride = c.pstride;
-    a.partials = partials + (c.red ? (pass & 1) * 3L * c.P : 0);
-    a.prev = partials + ((pass + 1) & 1) * 3L * c.P;
-    a.pass = pass;
     a.Vh = g.V / 2; a.Nx = g.Nx; a.Wh = g.Wt / 2;
-    a.xchunk = c.xchunk; a.G = c.G; a.NG = c.NG; a.NWT = c.NWT; a.NCH = c.NCH; a.P = c.P;
-    const dim3 grid((unsigned)(K * c.NWT * c.NCH)), block(64);
-    const bool xp = pass >= 2 && (pass & 1) == 0;
-    if (c.red) {
-        if (xp) hipLaunchKernelGGL((eo_batch_kernel<1, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((eo_batch_kernel<1, 0>), grid, block, 0, s, a);
-    } else {
-        if (xp) hipLaunchKernelGGL((eo_batch_kernel<0, 1>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((eo_batch_kernel<0, 0>), grid, block, 0, s, a);
-        hipLaunchKernelGGL(eo_batch_scalar_kernel, dim3(K), dim3(256), 0, s, c.P, partials, c.pstride, sc,
-                           pass == 0 ? 1 : 0);
-    }
-}
-
-void launch_eo_batch_flush(hipStream_t s, const EoBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
-                           long pass) {
-    if (!c.red) return;  // the scalar kernel has already evaluated the pass
-    hipLaunchKernelGGL(eo_batch_flush_kernel, dim3(K), dim3(64), 0, s, c.P, partials + (pass & 1) * 3L * c.P,
-                       c.pstride, sc, pass);
-}
-
-void launch_eo_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
-                              const double2 *d1, const double2 *d2, const CGScalars *sc) {
-    const long nb = (g.V + 255) / 256;
-    const int NBF = (int)(nb < 256 ? nb : 256);
-    hipLaunchKernelGGL(eob_finish_x_kernel, dim3(K * NBF), dim3(256), 0, s, NBF, g.V, x, d0, d1, d2, sc);
+    void (*const kern[2][2])(EOBArgs) = {{eo_batch_kernel<0, 0>, eo_batch_kernel<0, 1>},
+                                         {eo_batch_kernel<1, 0>, eo_batch_kernel<1, 1>}};
+    launch_batch_pass(s, c, K, pass, sc, partials, a, kern);
 }
 
 }  // namespace sm

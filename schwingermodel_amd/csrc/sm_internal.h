@@ -250,17 +250,35 @@ constexpr int kBatchRedMaxSlots = 512;   // redundant scalars up to this many pa
 // tiles per launch the tile height aims at: one resident round (256 CUs x 4 SIMDs x 2 waves at the
 // pass's 210-220 VGPRs); measured best of 1024..16384 at 64^2 and 256^2
 constexpr int kBatchTargetTiles = 2048;
-struct CGBatchCfg {
-    int NWT;        // wave tiles along t
+// Tiles, partial slots and scalar scheme of a batched solver, this one, the
+// even-odd one (below) and the mixed one's passes alike.
+struct BatchCfg {
+    int NWT;        // wave tiles along t (even-odd: along k)
     int G, NG;      // rows per granule, granules per column of tiles
     int P;          // partial slots per column (NWT * NG), 3 complex each
-    int red;        // 1: redundant scalars (every tile sums its column's previous partials)
+    int red;        // 1: redundant scalars (every tile sums its column's previous partials; P <= kBatchRedMaxSlots)
     int xchunk;     // rows per tile (a multiple of G)
     int NCH;        // tiles along x
     int NB0;        // blocks per column of the start kernel
     long pstride;   // complex per column in the partials buffer
 };
-CGBatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles = 0);
+// A solver's tiles of `width` owned columns on `extent` columns per row, granules of small_G
+// rows below Nx = 512 (8 from there), aiming at target_tiles tiles per launch
+BatchCfg batch_config(const Geometry &g, int K, int width, int extent, int small_G, int target_tiles);
+BatchCfg cg_batch_config(const Geometry &g, int K, int target_tiles = 0);
+// The scalar machinery of the fp64 batched solvers (one copy, sm_cgbatch.hip's
+// header has the scheme): the scalar step of pass `pass` without redundant
+// scalars; with them the last issued pass's state into sc for the host (else
+// nothing: the scalar kernel has evaluated it); the columns' scalars at the
+// start (tol, max_iter, S_-1) from the start kernel's partials; and, after the
+// last pass, x_b += alpha_{k-1} d_{k-1} on the columns of n complex whose
+// iteration count is odd.
+void launch_batch_scalars(hipStream_t s, const BatchCfg &c, int K, const double2 *partials, CGScalars *sc, long pass);
+void launch_batch_flush(hipStream_t s, const BatchCfg &c, int K, const double2 *partials, CGScalars *sc, long pass);
+void launch_batch_init_scalars(hipStream_t s, const BatchCfg &c, int K, const double2 *partials, CGScalars *sc,
+                               double tol, int max_iter);
+void launch_batch_finish_x(hipStream_t s, int K, long n, double2 *x, const double2 *d0, const double2 *d1,
+                           const double2 *d2, const CGScalars *sc);
 // The links and mass of each column: column b reads the field at U + b * ustride
 // (complex) and uses massv[b]. One field for all columns (sm_cg_batch, the
 // pion correlator): ustride = 0, massv = null and every column uses `mass`.
@@ -276,18 +294,13 @@ inline BatchLinks shared_links(const double2 *U, double mass) { return BatchLink
 void launch_batch_apply(hipStream_t s, const Geometry &g, int K, int dagger, const double2 *in, double2 *out,
                         const BatchLinks &l);
 // x = phi, T = D^dag phi, d0 = r_0 = phi - D T, and the columns' scalars (tol, max_iter, S_-1)
-void launch_cg_batch_init(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *phi, double2 *x,
+void launch_cg_batch_init(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *phi, double2 *x,
                           double2 *T, double2 *d0, const BatchLinks &l, double tol, int max_iter, double2 *partials,
                           CGScalars *sc);
 // pass j of every column that is not done (and, without redundant scalars, its scalar step)
-void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, const double2 *dold,
+void launch_cg_batch_pass(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *dold,
                           const double2 *rold, const double2 *aold, double2 *dnew, double2 *anew, double2 *x,
                           const BatchLinks &l, long pass, CGScalars *sc, double2 *partials);
-// redundant scalars: the last issued pass's state into sc for the host
-void launch_cg_batch_flush(hipStream_t s, const CGBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
-                           long pass);
-void launch_cg_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
-                              const double2 *d1, const double2 *d2, const CGScalars *sc);
 // ---- mixed-precision batched CG (sm_cgbatchsp.hip; driver sm_cgbatchmp.cpp) ----
 // Every launch serves the columns of `mask` (bit b = column b, K <= 64) and
 // leaves the others alone. The direction ring d[3] holds d_i of the running
@@ -295,7 +308,7 @@ void launch_cg_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *
 static_assert(kBatchMax <= 64, "the batched mixed-precision kernels name their columns in a 64-bit mask");
 // Pass `pass` of a round (0: the injected direction, no d store; even passes
 // >= 2 update y) and its scalar step, c's tiles; partials: K x 2 c.P complex.
-void launch_cg_batch_sp(hipStream_t s, const Geometry &g, const CGBatchCfg &c, int K, unsigned long long mask,
+void launch_cg_batch_sp(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, unsigned long long mask,
                         float2 *const d[3], float2 *const ad[2], float2 *y, const float2 *U32, double mass, long pass,
                         MPScalars *sc, double2 *partials);
 int batch_mp_blocks(const Geometry &g);  // blocks per column of the three kernels below (the lattice's alone)
@@ -420,17 +433,7 @@ void launch_pack_cb_faces4(hipStream_t s, const Geometry &g, const double2 *f, d
 // tiles per launch the tile height aims at: one resident round (256 CUs x 4 SIMDs x 1 wave at the
 // pass's register count)
 constexpr int kEoBatchTargetTiles = 1024;
-struct EoBatchCfg {
-    int NWT;        // wave tiles along k
-    int G, NG;      // rows per granule, granules per column of tiles
-    int P;          // partial slots per column (NWT * NG), 3 complex each
-    int red;        // 1: redundant scalars (P <= kBatchRedMaxSlots)
-    int xchunk;     // rows per tile (a multiple of G)
-    int NCH;        // tiles along x
-    int NB0;        // blocks per column of the start kernel
-    long pstride;   // complex per column in the partials buffer
-};
-EoBatchCfg eo_batch_config(const Geometry &g, int K, int target_tiles = 0);
+BatchCfg eo_batch_config(const Geometry &g, int K, int target_tiles = 0);  // BatchCfg, the scalar launchers: above
 // The checkerboard links and mass of each column: column b reads Ue / Uo + b * ustride
 // (complex) and uses massv[b]; ustride = 0 and massv = null: one field and `mass` for all.
 struct EoBatchLinks {
@@ -451,17 +454,13 @@ void launch_eob_hop(hipStream_t s, const Geometry &g, int K, int dagger, int p, 
 void launch_eob_dhat(hipStream_t s, const Geometry &g, int K, int dagger, const double2 *v, double2 *T, double2 *out,
                      const EoBatchLinks &l);
 // x = phi, d0 = r_0 = phi - Dhat Dhat^dag phi (T, W, A: work), and the columns' scalars
-void launch_eo_batch_init(hipStream_t s, const Geometry &g, const EoBatchCfg &c, int K, const double2 *phi, double2 *x,
+void launch_eo_batch_init(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *phi, double2 *x,
                           double2 *T, double2 *W, double2 *A, double2 *d0, const EoBatchLinks &l, double tol,
                           int max_iter, double2 *partials, CGScalars *sc);
 // pass j of every column that is not done (and, without redundant scalars, its scalar step)
-void launch_eo_batch_pass(hipStream_t s, const Geometry &g, const EoBatchCfg &c, int K, const double2 *d1,
+void launch_eo_batch_pass(hipStream_t s, const Geometry &g, const BatchCfg &c, int K, const double2 *d1,
                           const double2 *d2, const double2 *aold, double2 *dn, double2 *anew, double2 *x,
                           const EoBatchLinks &l, long pass, CGScalars *sc, double2 *partials);
-void launch_eo_batch_flush(hipStream_t s, const EoBatchCfg &c, int K, const double2 *partials, CGScalars *sc,
-                           long pass);
-void launch_eo_batch_finish_x(hipStream_t s, const Geometry &g, int K, double2 *x, const double2 *d0,
-                              const double2 *d1, const double2 *d2, const CGScalars *sc);
 
 // ---- mixed-precision even-odd CG (sm_eosp.hip; driver sm_eomp.cpp) ----
 // Pass `pass` of a segment on float2 checkerboard fields (0: the injected

@@ -16,7 +16,9 @@
 // the checks assert. Covered: segments that end at different passes with the early ones
 // idling, a column that converges at the first update while others go on, a bad column
 // that falls back alone, two failed updates on one column only, the iteration limit per
-// column, the forced fallback, K = 1 and K = 64. tol 1e-10, |phi| = 1 throughout.
+// column, the forced fallback, K = 1 and K = 64. tol 1e-10, |phi| = 1 throughout. And the
+// K-column chunk loop under the rounds (cg_chunked_columns, which the fp64 batched hosts
+// run as well) on a fixed script, its chunk sizes as literals.
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
@@ -337,7 +339,64 @@ static void check_endless_segment() {  // a device that never ends a segment is 
     CHECK(last_error == o.stuck && o.issued == 41);
 }
 
+// The K-column chunk loop itself (cg_chunked_columns), driven directly: three columns whose
+// residuals fall at 0.5, at 0.6 then 0.9 from k = 10, and at 0.8 then 0.97 from k = 12, to the
+// target 1e-3, which they pass at k = 10, 28 and 151: a column is done from pass k + 1 on. The
+// chunk sizes are literals from a separate copy of the hosts' loop run on this script, not
+// from cg_chunked_columns: 4, then 8 (no rate yet), then the slowest running column's wish.
+static void check_chunk_loop() {
+    auto err = [](int b, int k) {
+        const double r1[3] = {0.5, 0.6, 0.8}, r2[3] = {0.5, 0.9, 0.97};
+        const int kink[3] = {10, 10, 12};
+        return k <= kink[b] ? std::pow(r1[b], (double)k) : std::pow(r1[b], (double)kink[b]) * std::pow(r2[b], (double)(k - kink[b]));
+    };
+    const int kend[3] = {10, 28, 151};
+    for (int b = 0; b < 3; ++b) CHECK(err(b, kend[b]) < 1e-3 && err(b, kend[b] - 1) >= 1e-3);
+    std::vector<long> chunks, reads;
+    long passes = 0;
+    bool ended = false;
+    int last_running = -1;
+    CHECK(sm_host::cg_chunked_columns(
+              3, 1001,
+              [&](long j, long nb) {
+                  CHECK(j == passes);
+                  passes += nb;
+                  chunks.push_back(nb);
+                  return SM_OK;
+              },
+              [&](long issued) {
+                  CHECK(issued == passes);
+                  reads.push_back(issued);
+                  return SM_OK;
+              },
+              [&](int b) {
+                  const int k = (int)std::min<long>(passes - 1, kend[b]);
+                  return sm_host::CgStatus{k, err(b, k), 1e-3, passes - 1 >= kend[b]};
+              },
+              [&](long issued, int running, int) {
+                  CHECK(issued == passes);
+                  last_running = running;
+              },
+              &ended) == SM_OK);
+    CHECK(chunks == (std::vector<long>{4, 8, 22, 98, 22}));
+    CHECK(reads == (std::vector<long>{4, 12, 34, 132, 154}));
+    CHECK(ended && last_running == 0);
+    // the limit ends the loop with columns running: the last chunk is cut, *ended is false
+    chunks.clear();
+    passes = 0;
+    CHECK(sm_host::cg_chunked_columns(
+              3, 40, [&](long, long nb) { passes += nb; chunks.push_back(nb); return SM_OK; }, [&](long) { return SM_OK; },
+              [&](int b) {
+                  const int k = (int)std::min<long>(passes - 1, kend[b]);
+                  return sm_host::CgStatus{k, err(b, k), 1e-3, passes - 1 >= kend[b]};
+              },
+              [&](long, int running, int) { last_running = running; }, &ended) == SM_OK);
+    CHECK(chunks == (std::vector<long>{4, 8, 22, 6}));
+    CHECK(!ended && last_running == 1);
+}
+
 int main() {
+    check_chunk_loop();
     check_idling();
     check_early_convergence();
     check_bad_column_alone();
