@@ -591,6 +591,24 @@ int sm_cg_batch_mixed_last(const sm_ctx *ctx, int K, sm_cg_mixed_info *out /* K 
 int sm_pion_correlator(sm_ctx *ctx, double m0, double tol, int max_iter, int nsrc, const int *src_x,
                        const int *src_t, double *C /* nsrc*Nt, host */, sm_cg_result *res /* 2*nsrc, nullable */);
 
+/* The solve inside sm_pion_correlator: 0 = D D^dag as described above (default;
+ * that code path, unchanged), 1 = through the even-odd system; < 0 keeps.
+ * *mode_out (nullable) = current. SM_ERR_ARG (mode stays as it was) for mode 1
+ * on sharded, host-staged, loopback and peer contexts and for other values.
+ * Mode 1, with m = m0 + 2, D = m - H/2 and Dhat = m - (1/4m) H_eo H_oe, for all
+ * 2 nsrc columns at once, every stage one launch:
+ *   phihat_e = phi_e + (1/2m) H_eo phi_o,  X = (Dhat Dhat^dag)^-1 phihat_e
+ *   (sm_eo_cg_batch's solver, about 0.4-0.5x the iterations of D D^dag),
+ *   S_e = Dhat^dag X,  S_o = (1/m) phi_o + (1/2m) H_oe S_e,
+ * then the same slice sums. res reports the even-odd solves (the stop test is
+ * ||r|| < tol ||phihat_e||). Always fp64, whatever sm_cg_batch_precision says.
+ * C and res are bitwise sm_ens_pion_correlator's with solver 1 on the same
+ * field and mass. Odd Nx or Nt in mode 1 fails sm_pion_correlator (not this
+ * switch) with SM_ERR_ARG; mode 0 keeps working. Memory in mode 1: sm_eo_cg_batch's
+ * workspace plus 112 B per site and column of half-lattice fields and
+ * propagators, from the first such call on. */
+int sm_pion_solver(sm_ctx *ctx, int mode, int *mode_out);
+
 /* ==== batched even-odd CG ====================================================
  * Dhat Dhat^dag x_b = phi_b on the even sites for K right-hand sides on the
  * context's current gauge field, ONE launch per iteration for the whole batch
@@ -697,6 +715,35 @@ int sm_ens_fill_gauge(sm_ens *e, int r, uint64_t seed, double sigma);
 /* sp[r] = sum Re U_01, gauge_action[r] = beta[r] sum Re(1 - U_01) of replica r:
  * one launch and one synchronisation for all R, bitwise sm_plaquette's values */
 int sm_ens_plaquette(sm_ens *e, const double *beta /* R */, double *sp /* R */, double *gauge_action /* R */);
+/* The pion correlator of every replica on its current field with its own mass
+ * m0[r], from nsrc point sources common to all replicas; the definitions are
+ * sm_pion_correlator's (unit vector at (src_x[s], src_t[s]) of plane a, S_a =
+ * D^-1 phi, absolute t). C[(r*nsrc + s)*Nt + t]; res[(r*nsrc + s)*2 + a]
+ * (nullable). For each (source, spin) pair ONE batched solve of R columns,
+ * column r on replica r's links and mass, and one slice launch per source for
+ * all replicas.
+ * solver 0: y = (D D^dag)^-1 phi, S = D^dag y. Replica r's C and res are
+ * bitwise what sm_pion_correlator (default settings) returns on a lone context
+ * holding the same field with m0[r].
+ * solver 1: the even-odd system as under sm_pion_solver; res reports the
+ * even-odd solves. Needs even Nx and Nt: SM_ERR_ARG naming the checkerboard
+ * otherwise, and the ensemble stays usable for solver 0. Its fields are those
+ * of the even-odd action, allocated at first use.
+ * A replica's C and res depend on its field, its mass and the arguments only:
+ * bitwise the same at R = 1, at any position and next to any neighbours; fixed
+ * summation order, no atomics, so repeated calls agree bitwise. Always fp64:
+ * none of the precision switches reaches it. It works in the ensemble's chi,
+ * phi, x and solver workspaces, free between trajectories; new memory is the
+ * source coordinates and C on the device. A trajectory after a measurement is
+ * bitwise the trajectory without it; the context's gauge field, solvers and
+ * sm_pion_correlator are untouched. SM_ERR_ARG for a null ensemble, m0, src_*
+ * or C, solver not 0 or 1, nsrc < 1 or 2 nsrc > sm_cg_batch_max(), a
+ * coordinate outside the lattice, max_iter < 0; SM_ERR_STATE while some replica
+ * has no gauge field; SM_ERR_HIP naming the bytes when an allocation fails (the
+ * ensemble stays usable). Synchronous. */
+int sm_ens_pion_correlator(sm_ens *e, const double *m0 /* R */, double tol, int max_iter, int solver, int nsrc,
+                           const int *src_x, const int *src_t, double *C /* R*nsrc*Nt, host */,
+                           sm_cg_result *res /* R*2*nsrc, nullable */);
 int sm_ens_hmc_trajectory(sm_ens *e, const sm_hmc_params *p /* R */, uint64_t traj, sm_hmc_result *out /* R */);
 /* sm_hmc_run per replica (the reference's statistics and acceptance
  * definition; out[r].cg_link_bytes = 32). The series are R rows of Nmeas.

@@ -237,6 +237,20 @@ class Lattice:
         self._batch_K = 2 * n
         return C, list(res)
 
+    PION_SOLVERS = {"plain": 0, "even_odd": 1}
+
+    def pion_solver(self, mode=None):
+        """Set ("plain" / "even_odd", or 0 / 1) and return the solve inside
+        pion_correlator (sm_pion_solver; None only reads): D D^dag, or the
+        even-odd system with about half the iterations (always fp64, even Nx
+        and Nt). One-shard contexts only."""
+        m = -1 if mode is None else self.PION_SOLVERS.get(mode, mode)
+        if not isinstance(m, int):
+            raise ValueError(f"pion solver {mode!r}: 'plain' or 'even_odd'")
+        cur = ctypes.c_int()
+        check(lib.sm_pion_solver(self.ctx, m, ctypes.byref(cur)))
+        return "even_odd" if cur.value == 1 else "plain"
+
     def ensemble(self, R):
         """An Ensemble of R independent HMC chains on this lattice, evolved in
         lockstep with one launch per step for all of them (sm_ens_create)."""
@@ -339,6 +353,31 @@ class Ensemble:
         sp, act = np.empty(self.R), np.empty(self.R)
         check(lib.sm_ens_plaquette(self.ens, _vp(b), _vp(sp), _vp(act)))
         return sp, act
+
+    def pion_correlator(self, m0s, sources, solver="plain", tol=None, max_iter=None):
+        """The pion correlator of every replica on its current field with its
+        own mass m0s[r], from point sources common to all replicas
+        (sm_ens_pion_correlator). sources: a list of (x, t); solver: "plain"
+        (D D^dag; bitwise Lattice.pion_correlator on a lone context with that
+        field) or "even_odd". Returns (C, results): C of shape (R, nsrc, Nt),
+        results[r][2 * s + a] the solve of replica r, source s, spin a."""
+        m = np.ascontiguousarray(m0s, dtype=np.float64)
+        if m.shape != (self.R,):
+            raise ValueError(f"ensemble: {m.size} masses for {self.R} replicas")
+        mode = Lattice.PION_SOLVERS.get(solver, solver)
+        if not isinstance(mode, int) or isinstance(mode, bool) or mode not in (0, 1):
+            raise ValueError(f"ensemble: pion solver {solver!r}: 'plain' or 'even_odd'")
+        src = [(int(x), int(t)) for x, t in sources]
+        n = len(src)
+        sx = (ctypes.c_int * max(n, 1))(*[s[0] for s in src])
+        st = (ctypes.c_int * max(n, 1))(*[s[1] for s in src])
+        Nt = self.lattice.Wt
+        C = np.zeros((self.R, max(n, 1), Nt))
+        res = (CGResult * (self.R * max(2 * n, 1)))()
+        check(lib.sm_ens_pion_correlator(self.ens, _vp(m), float(CG.tol if tol is None else tol),
+                                         int(CG.max_iter if max_iter is None else max_iter), mode, n, sx, st, _vp(C),
+                                         res))
+        return C, [list(res[r * 2 * n:(r + 1) * 2 * n]) for r in range(self.R)]
 
     def trajectory(self, params, traj):
         """One HMC update of every replica (sm_ens_hmc_trajectory): params is a

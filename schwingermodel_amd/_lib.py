@@ -153,6 +153,7 @@ def _load():
         "sm_cg_batch_mixed_last": ([vp, ci, ctypes.POINTER(CGMixedInfo)], ci),
         "sm_pion_correlator": ([vp, cd, cd, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp,
                                 ctypes.POINTER(CGResult)], ci),
+        "sm_pion_solver": ([vp, ci, ctypes.POINTER(ci)], ci),
         # replica ensemble: R HMC chains in lockstep
         "sm_ens_max": ([], ci),
         "sm_ens_create": ([vp, ci, ctypes.POINTER(vp)], ci),
@@ -162,6 +163,8 @@ def _load():
         "sm_ens_download_gauge": ([vp, ci, vp, vp], ci),
         "sm_ens_fill_gauge": ([vp, ci, u64, cd], ci),
         "sm_ens_plaquette": ([vp, vp, vp, vp], ci),
+        "sm_ens_pion_correlator": ([vp, vp, cd, ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), vp,
+                                    ctypes.POINTER(CGResult)], ci),
         "sm_ens_hmc_trajectory": ([vp, ctypes.POINTER(HMCParams), u64, ctypes.POINTER(HMCResult)], ci),
         "sm_ens_hmc_run": ([vp, ctypes.POINTER(HMCParams), ci, u64, ci, ci, ci, ctypes.c_char_p,
                             ctypes.POINTER(HMCSummary), vp, vp], ci),

@@ -20,6 +20,8 @@
 // and scalars as they left them. The gauge field is read from c->U at every
 // call and nothing derived from it is kept, so uploads and HMC trajectories
 // between two batched solves need no call.
+// sm_pion_solver = 1 hands sm_pion_correlator's body to the even-odd path of
+// sm_pion.cpp after the argument checks; mode 0 is the code below.
 
 #include <hip/hip_runtime.h>
 
@@ -200,9 +202,13 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
         if (src_x[s] < 0 || src_x[s] >= c->g.Nx || src_t[s] < 0 || src_t[s] >= c->g.Wt)
             return fail(SM_ERR_ARG, "pion correlator: source %d at (%d, %d) outside the %d x %d lattice", s, src_x[s],
                         src_t[s], c->g.Nx, c->g.Wt);
+    const bool eo = c->pion_solver == 1;  // sm_pion_solver: the even-odd path (sm_pion.cpp)
+    if (eo && (c->g.Nx % 2 || c->g.Wt % 2))
+        return fail(SM_ERR_ARG, "pion correlator: the even-odd solve (sm_pion_solver = 1) needs even Nx and Nt (%d x %d): "
+                    "an odd periodic lattice has no checkerboard", c->g.Nx, c->g.Wt);
     TRY(check_ready(c));
     HIP_TRY(hipSetDevice(c->device));
-    TRY(staging_ready(c, K));
+    if (!eo) TRY(staging_ready(c, K));
     if (!c->bt_src) TRY(alloc_dev((void **)&c->bt_src, sizeof(int) * kBatchMax, kBatchWho, "source coordinates"));
     if (!c->bt_C) TRY(alloc_dev((void **)&c->bt_C, sizeof(double) * (kBatchMax / 2) * (size_t)c->g.Wt, kBatchWho,
                                    "correlator"));
@@ -211,6 +217,7 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
     // pageable host memory: the copies have left the caller's arrays when they return
     HIP_TRY(hipMemcpyAsync(sx, src_x, sizeof(int) * (size_t)nsrc, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(st, src_t, sizeof(int) * (size_t)nsrc, hipMemcpyHostToDevice, c->stream));
+    if (eo) return pion_correlator_eo(c, m0, tol, max_iter, nsrc, sx, st, C, res);
     HIP_TRY(hipMemsetAsync(c->bt_phi, 0, fb, c->stream));
     launch_point_sources(c->stream, c->g, K, sx, st, c->bt_phi);
     HIP_TRY(hipGetLastError());

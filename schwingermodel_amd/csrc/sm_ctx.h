@@ -277,6 +277,13 @@ struct sm_ctx {
     double2 *eob_phi = nullptr, *eob_x = nullptr;    // eob_K x V complex
     double2 *eob_fphi = nullptr, *eob_fx = nullptr;  // eob_fK x 2V complex
 
+    // sm_pion_correlator through the even-odd system (sm_pion_solver = 1; sm_pion.cpp):
+    // five half-lattice fields and the full-layout propagators for pn_K columns, from
+    // the first such call on. The solve runs on eob and eob_U (above).
+    int pion_solver = 0;
+    int pn_K = 0;
+    double2 *pn_buf = nullptr;      // pn_K x 7V complex
+
     double2 *field(int i) { return fields[i]; }
 };
 
@@ -461,6 +468,20 @@ int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, doubl
                    double tol, int max_iter, sm_cg_result *res);
 void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's (sm_cgbatch.cpp)
 void eo_batch_free(sm_ctx *c);
+// The context's even-odd batch workspace for K columns and its checkerboard link buffer (sm_eobatch.cpp)
+int eob_ready(sm_ctx *c, int K);
+// ---- the pion correlator's even-odd path (sm_pion.cpp) ----
+// S_b = D^-1 phi_b for K point sources through the even-odd system, every stage
+// one launch for all K columns: phihat_e = phi_e + (1/2m) H_eo phi_o, X =
+// (Dhat Dhat^dag)^-1 phihat_e (eo_batch_solve on w and l, reported in res),
+// S_e = Dhat^dag X, S_o = (1/m) phi_o + (1/2m) H_oe S_e. eh: five half-lattice
+// fields of K x V complex; S: K full-layout columns.
+int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src, double2 *eh, const EoBatchLinks &l,
+                        double tol, int max_iter, sm_cg_result *res, double2 *S);
+// sm_pion_correlator's body in mode 1 (arguments checked by the caller; sx / st: device)
+int pion_correlator_eo(sm_ctx *c, double m0, double tol, int max_iter, int nsrc, const int *sx, const int *st,
+                       double *C, sm_cg_result *res);
+void pion_free(sm_ctx *c);
 // The mixed-precision batched solve on the context's gauge field (sm_cgbatchmp.cpp):
 // K columns of phi -> x on the device, c->bt_info[b] = column b's report.
 int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,

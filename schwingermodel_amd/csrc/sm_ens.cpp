@@ -27,13 +27,17 @@
 //
 // One-shard contexts, always fp64. Kernels: sm_gauge.hip, sm_kernels.hip
 // (ens_*), sm_cgbatch.hip, sm_eobatch.hip. Host bookkeeping that needs no
-// device: sm_ens_host.h.
+// device: sm_ens_host.h. The state itself (struct sm_ens) is in sm_ens.h, which
+// the measurements of sm_pion.cpp share; they work in chi, phi, x and the solver
+// workspaces between trajectories and write nothing a trajectory reads before
+// writing it.
 #include <hip/hip_runtime.h>
 
 #include <string>
 #include <vector>
 
 #include "sm_ctx.h"
+#include "sm_ens.h"
 #include "sm_ens_host.h"
 #include "sm_fields.h"
 #include "sm_internal.h"
@@ -41,63 +45,14 @@
 using namespace sm;
 using namespace sm_host;
 
-struct sm_ens {
-    sm_ctx *c = nullptr;
-    int R = 0;
-    double2 *U = nullptr, *Ubak = nullptr;                  // R x 2V complex
-    double2 *chi = nullptr, *phi = nullptr, *x = nullptr;   // chi doubles as T = D^dag psi of the force
-    double *P = nullptr, *F = nullptr;                      // R x 2V doubles
-    BatchWs ws;
-    EnsPar *par = nullptr, *h_par = nullptr;                // device, pinned host
-    double *massv = nullptr, *h_mass = nullptr;             // m0 + 2 per replica
-    double2 *part = nullptr;                                // 3 x R x gauge_reduce_blocks partials
-    double2 *sums = nullptr, *h_sums = nullptr;             // 3 x R
-    std::vector<char> have;                                 // replica r holds a gauge field
-    // even-odd action, from the first even-odd trajectory on
-    BatchWs eows;
-    double2 *Ucb = nullptr;                                 // even links R x V complex, then odd links R x V
-    double2 *eh = nullptr;                                  // EH_N half-lattice fields, R x V complex each
-};
+namespace sm_host {
 
-namespace {
-
-struct HTerms {
-    double H, sp, action;
-    int iterations, converged;
-};
-
-size_t slab_complex(const sm_ens *e) { return 2 * (size_t)e->c->g.V; }
-
-// half-lattice fields of the even-odd action: phi_e, X, Y = Dhat^dag X, the odd
-// work field of Dhat, l_o (chi_e during the heat bath), r_o
-enum { EH_PHI, EH_X, EH_Y, EH_T, EH_LO, EH_RO, EH_N };
-double2 *eh(const sm_ens *e, int i) { return e->eh + (size_t)i * (size_t)e->R * (size_t)e->c->g.V; }
-
-void ens_free(sm_ens *e) {
-    void *dev[] = {e->U, e->Ubak, e->chi, e->phi, e->x,   e->P,  e->F,
-                   e->par, e->massv, e->part, e->sums, e->Ucb, e->eh};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *host[] = {e->h_par, e->h_mass, e->h_sums};
-    for (void *p : host)
-        if (p) (void)hipHostFree(p);
-    batch_ws_free(e->ws);
-    batch_ws_free(e->eows);
-    delete e;
-}
-
-int ens_alloc(void **p, size_t bytes, const char *what, bool pinned = false) {
+int ens_alloc(void **p, size_t bytes, const char *what, bool pinned) {
     const hipError_t err = pinned ? hipHostMalloc(p, bytes) : hipMalloc(p, bytes);
     if (err == hipSuccess) return SM_OK;
     *p = nullptr;
     (void)hipGetLastError();
     return fail(SM_ERR_HIP, "ensemble: allocating %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(err));
-}
-
-int ens_check(const sm_ens *e, int r) {
-    if (!e) return fail(SM_ERR_ARG, "null ensemble");
-    if (r < 0 || r >= e->R) return fail(SM_ERR_ARG, "ensemble: replica %d outside 0..%d", r, e->R - 1);
-    return SM_OK;
 }
 
 int all_have(const sm_ens *e) {
@@ -106,13 +61,6 @@ int all_have(const sm_ens *e) {
             return fail(SM_ERR_STATE, "ensemble: replica %d has no gauge field (sm_ens_upload_gauge / sm_ens_fill_gauge)",
                         r);
     return SM_OK;
-}
-
-BatchLinks links(const sm_ens *e) { return BatchLinks{e->U, (long)slab_complex(e), 0.0, e->massv}; }
-
-EoBatchLinks eo_links(const sm_ens *e) {
-    const long V = e->c->g.V;
-    return EoBatchLinks{e->Ucb, e->Ucb + (size_t)e->R * V, V, 0.0, e->massv};
 }
 
 // The even-odd action's fields: 32 B per site and replica of checkerboard
@@ -131,6 +79,34 @@ int eo_fields_ready(sm_ens *e) {
         batch_ws_free(e->eows);
         return rc;
     }
+    return SM_OK;
+}
+
+}  // namespace sm_host
+
+namespace {
+
+struct HTerms {
+    double H, sp, action;
+    int iterations, converged;
+};
+
+void ens_free(sm_ens *e) {
+    void *dev[] = {e->U, e->Ubak, e->chi, e->phi, e->x,   e->P,  e->F,
+                   e->par, e->massv, e->part, e->sums, e->Ucb, e->eh, e->pn_src, e->pn_C};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    void *host[] = {e->h_par, e->h_mass, e->h_sums};
+    for (void *p : host)
+        if (p) (void)hipHostFree(p);
+    batch_ws_free(e->ws);
+    batch_ws_free(e->eows);
+    delete e;
+}
+
+int ens_check(const sm_ens *e, int r) {
+    if (!e) return fail(SM_ERR_ARG, "null ensemble");
+    if (r < 0 || r >= e->R) return fail(SM_ERR_ARG, "ensemble: replica %d outside 0..%d", r, e->R - 1);
     return SM_OK;
 }
 

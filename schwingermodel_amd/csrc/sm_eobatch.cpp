@@ -55,7 +55,7 @@ int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, doubl
 }
 
 // The context's own workspace and half-lattice staging: kept while K fits, regrown else.
-static int eob_ready(sm_ctx *c, int K) {
+int eob_ready(sm_ctx *c, int K) {
     HIP_TRY(hipSetDevice(c->device));
     if (c->eob.K < K)
         TRY(batch_ws_alloc(c, c->eob, K, c->g.V, eo_batch_config(c->g, K, c->eob_tiles).pstride, kEoBatchWho));

@@ -462,6 +462,27 @@ void launch_eo_batch_pass(hipStream_t s, const Geometry &g, const BatchCfg &c, i
                           const double2 *d2, const double2 *aold, double2 *dn, double2 *anew, double2 *x,
                           const EoBatchLinks &l, long pass, CGScalars *sc, double2 *partials);
 
+// ---- pion correlator of K columns / R replicas (sm_pion.hip; host sm_pion.cpp) ----
+// Which point source each of K columns carries: sx / st (device) hold the
+// sources' coordinates; per_col: column k = source k / 2, spin k % 2 (the
+// context's correlator), else source s0, spin a0 in every column (one column
+// per replica).
+struct PionCols {
+    const int *sx, *st;
+    int s0, a0, per_col;
+};
+// The unit vectors into zeroed fields: full != null: K full-layout columns (2V
+// complex apart); else K checkerboard columns (V complex apart), e or o by the site's parity.
+void launch_pion_sources(hipStream_t s, const Geometry &g, int K, const PionCols &src, double2 *full, double2 *e,
+                         double2 *o);
+// out_b += a_b (inv_mass = 0) or out_b += a_b / m_b (1) on K half-lattice columns, m_b column b's mass of l
+void launch_pion_eo_add(hipStream_t s, const Geometry &g, int K, int inv_mass, const double2 *a, double2 *out,
+                        const EoBatchLinks &l);
+// C[r * cstride + t] = the slice sums of replica r's spin-0 / spin-1 propagators A_r, B_r (R full-layout
+// columns each), added in launch_pion_slices' order
+void launch_ens_pion_slices(hipStream_t s, const Geometry &g, int R, const double2 *A, const double2 *B, double *C,
+                            long cstride);
+
 // ---- mixed-precision even-odd CG (sm_eosp.hip; driver sm_eomp.cpp) ----
 // Pass `pass` of a segment on float2 checkerboard fields (0: the injected
 // direction, no d store; even passes >= 2 update y): d_{j-1} in d1, d_{j-2} in
