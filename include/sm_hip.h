@@ -162,7 +162,9 @@ int sm_comm_info(const sm_ctx *ctx, int *transport, int *nranks, int *rank);
 int sm_cg_sums_in_pass(const sm_ctx *ctx, int *in_pass);
 int sm_synchronize(sm_ctx *ctx);
 /* Launch-geometry knobs of the stencil kernels (tuning / A-B benchmarks):
- * bt = t-columns per block (64, 128, 256), xchunk = rows marched per block,
+ * bt = t-columns per block (64, 128, 192 or 256: whole waves up to 256
+ * threads; anything else is SM_ERR_ARG and leaves the setting as it was),
+ * xchunk = rows marched per block (>= 1; may exceed Nx),
  * xcd_remap = 1 maps the tiles one XCD receives to x-adjacent tiles,
  * variant selects the stencil code variant. Values <= 0 (< 0 for xcd_remap
  * and variant) keep the current setting. */
