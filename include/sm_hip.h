@@ -755,6 +755,70 @@ int sm_ens_hmc_run(sm_ens *e, const sm_hmc_params *p /* R */, int hot_start, uin
                    int Nmeas, int Nsteps, const char *save_prefix, sm_hmc_summary *out /* R */,
                    double *sp_series /* R*Nmeas, nullable */, double *gs_series /* R*Nmeas, nullable */);
 
+/* ==== topological charge and Wilson flow ======================================
+ * Gauge observables beyond the plaquette, for a context's field and for every
+ * replica of an ensemble (schwingermodel_amd/csrc/sm_flow.cpp, sm_flow.hip).
+ * Not in the reference, which measures the plaquette only; conventions are
+ * those of sm_plaquette (plane 0 = U_t, plane 1 = U_x, U_01 the same
+ * expression in the same order). One pass over the field gives
+ *   action = sum_n (1 - Re U_01(n))          (beta = 1; the caller scales it)
+ *   q_geo  = (1/2 pi) sum_n atan2(Im U_01(n), Re U_01(n))
+ *   q_sin  = (1/2 pi) sum_n Im U_01(n)
+ * q_geo is the geometric charge, an integer up to rounding on any field;
+ * q_sin the field-theoretic one, which approaches q_geo under flow. The sums
+ * run in sm_plaquette's grid and order without atomics: repeated calls agree
+ * bitwise, and action is bitwise sm_plaquette's gauge_action at beta = 1.
+ * The flow integrates d theta_mu(n) / dt = -d/d theta_mu(n) sum (1 - Re U_01),
+ * whose right-hand side Z_mu(n) = -Im(U_mu(n) conj(S_mu(n))) is sm_gauge_force
+ * at beta = 1 (S: sm_staples), by Luescher's third-order scheme in its
+ * one-accumulator form; one step of size eps, A one double per link:
+ *   A = eps Z(W);                        W <- W exp(i A / 4)
+ *   A = (8/9) eps Z(W) - (17/36) A;      W <- W exp(i A)
+ *   A = (3/4) eps Z(W) - A;              W <- W exp(i A)
+ * with exp(i y) = (cos y, sin y) and the plain complex product, as the
+ * leapfrog's link update. Each stage is ONE fused launch (both staple forces,
+ * the accumulator, both rotated links, written to the other of two field
+ * buffers; 80-96 B of traffic per site), for all replicas of an ensemble.
+ * series[k], k = 0 .. sm_flow_points(p) - 1: the three sums after
+ * k * meas_every steps, at flow time t = k * meas_every * eps; point 0 is the
+ * unflowed field, and nsteps = 0 is one point and no stage (bitwise
+ * sm_topology). Every stage and measurement of a flow is enqueued at once; the
+ * sums collect on the device and one copy brings them back: about 3 nsteps
+ * launches plus two per point, no host round trip in between.
+ * A flow is a measurement: the context's gauge field, the ensemble's fields
+ * and every solver workspace are bitwise what they were before the call, and
+ * a trajectory or a solve after a flow is bitwise the one without it. The
+ * context flows in two field buffers and an accumulator of its own, allocated
+ * at its first flow with nsteps > 0 and freed by sm_destroy: 80 B per site (2 x
+ * 32 + 16), plus 24 B per measured point. The ensemble flows in its kept-field
+ * backup, chi and momenta, free between trajectories: its new memory is 24 B
+ * per replica and point.
+ * Replica r's values, series and flowed field are bitwise those of a lone
+ * one-shard context holding the same field: the same at R = 1, at any position
+ * and next to any neighbours.
+ * sm_topology works on every context sm_plaquette works on (t-sharded,
+ * host-staged, loopback, peer; the same ghost links and global sums; every
+ * shard receives the global values). The two flow calls are for one-shard
+ * contexts: SM_ERR_ARG naming the restriction on sharded, host-staged,
+ * loopback and peer contexts (not in this version: the stages would need a
+ * ghost exchange of a field that is not the context's U). SM_ERR_ARG also for
+ * null pointers (U0_out / U1_out: both or neither), eps <= 0 or not finite,
+ * nsteps < 0, meas_every < 1; SM_ERR_STATE before a gauge upload or while some
+ * replica has no field; SM_ERR_HIP naming the bytes asked for when an
+ * allocation fails, after which the context or ensemble stays usable. Always
+ * fp64. All four calls are synchronous.
+ * Not in this version: flow on t-shards, a charge column in sm_hmc_run /
+ * sm_ens_hmc_run, mixed precision, other smearings. */
+typedef struct { double action, q_geo, q_sin; } sm_topo;
+typedef struct { double eps; int nsteps; int meas_every; } sm_flow_params;
+int sm_flow_points(const sm_flow_params *p);   /* 1 + nsteps / meas_every; < 0 for bad params */
+int sm_topology(sm_ctx *ctx, sm_topo *out);
+int sm_wilson_flow(sm_ctx *ctx, const sm_flow_params *p, sm_topo *series /* points */,
+                   double *U0_out, double *U1_out /* nullable: the flowed field, host */);
+int sm_ens_topology(sm_ens *e, sm_topo *out /* R */);
+int sm_ens_wilson_flow(sm_ens *e, const sm_flow_params *p, sm_topo *series /* R * points, replica-major */,
+                       double *U_out /* nullable, host: R x (plane 0, plane 1) of V complex */);
+
 /* Gather the sharded gauge field to shard 0 (SaveConf's MPI_Gatherv,
  * src/gauge_conf.cpp:378-396): U0/U1 on shard 0 receive the global
  * Nx x Nt field (n = x*Nt + t); other shards may pass NULL. RCCL transport

@@ -21,15 +21,18 @@ The lattice geometry (the reference's compile-time NS/NT plus mpi::) is set
 once with init(Nx, Nt, nshard, shard, device, unique_id). There is no CPU
 fallback: without the HIP library or a GPU every call raises.
 """
+import collections
 import ctypes
+import math
 
 import numpy as np
 
-from ._lib import CGMixedInfo, CGResult, HamiltonianTerms, HMCParams, HMCResult, HMCSummary, SMError, check, lib
+from ._lib import (CGMixedInfo, CGResult, FlowParams, HamiltonianTerms, HMCParams, HMCResult, HMCSummary, SMError,
+                   Topo, check, lib)
 
 __all__ = ["spinor", "re_field", "c_double", "I_number", "CG", "init", "lattice", "Lattice", "Ensemble",
            "D_phi", "D_dagger_phi", "D_D_dagger_phi", "phi_dag_partialD_phi",
-           "conjugate_gradient", "dot", "SMError", "CGResult", "lib", "check"]
+           "conjugate_gradient", "dot", "SMError", "CGResult", "lib", "check", "Topology", "FlowSeries"]
 
 c_double = complex
 I_number = complex(0.0, 1.0)
@@ -44,6 +47,34 @@ class CG:
 
 def _vp(a):
     return ctypes.c_void_p(a.ctypes.data)
+
+
+# What topology() / wilson_flow() return: float arrays, 0-d for a lattice's
+# topology, (R,) for an ensemble's; a flow's have one more axis, the measured
+# points, and t is the flow time of each (include/sm_hip.h "topological charge
+# and Wilson flow").
+Topology = collections.namedtuple("Topology", "action q_geo q_sin")
+FlowSeries = collections.namedtuple("FlowSeries", "t action q_geo q_sin")
+
+
+def _flow_params(eps, nsteps, meas_every):
+    """(FlowParams, points) of a Wilson flow, checked as sm_wilson_flow checks them."""
+    if isinstance(eps, bool) or not isinstance(eps, (int, float, np.integer, np.floating)):
+        raise TypeError(f"wilson_flow: eps = {eps!r}, expected a number")
+    if not math.isfinite(eps) or not eps > 0:
+        raise ValueError(f"wilson_flow: eps = {eps!r}, expected a finite step > 0")
+    for name, v, lo in (("nsteps", nsteps, 0), ("meas_every", meas_every, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise TypeError(f"wilson_flow: {name} = {v!r}, expected an integer")
+        if v < lo or v > 2**31 - 2:
+            raise ValueError(f"wilson_flow: {name} = {v!r}, expected an integer >= {lo}")
+    return FlowParams(float(eps), int(nsteps), int(meas_every)), 1 + int(nsteps) // int(meas_every)
+
+
+def _topo_arrays(buf, shape):
+    """The (action, q_geo, q_sin) arrays of a ctypes array of sm_topo laid out as `shape`."""
+    a = np.ctypeslib.as_array(buf).view(np.float64).reshape(shape + (3,))
+    return tuple(np.array(a[..., i]) for i in range(3))
 
 
 class spinor:
@@ -251,6 +282,31 @@ class Lattice:
         check(lib.sm_pion_solver(self.ctx, m, ctypes.byref(cur)))
         return "even_odd" if cur.value == 1 else "plain"
 
+    def topology(self):
+        """Topology(action, q_geo, q_sin) of the context's current gauge field
+        (sm_topology; 0-d float arrays): sum (1 - Re U_01), the geometric charge
+        (1/2 pi) sum arg U_01 and the field-theoretic one (1/2 pi) sum Im U_01.
+        Works on every context plaquette sums work on; global values."""
+        out = (Topo * 1)()
+        check(lib.sm_topology(self.ctx, out))
+        return Topology(*_topo_arrays(out, ()))
+
+    def wilson_flow(self, eps, nsteps, meas_every=1, return_field=False):
+        """Wilson flow of the current gauge field by nsteps third-order steps of
+        size eps (sm_wilson_flow; the context's field is not changed). Returns
+        FlowSeries(t, action, q_geo, q_sin), arrays of 1 + nsteps // meas_every
+        points: the unflowed field, then every meas_every steps. With
+        return_field also the flowed field, complex128 of shape (2, V).
+        One-shard contexts."""
+        p, points = _flow_params(eps, nsteps, meas_every)
+        series = (Topo * points)()
+        U = np.empty((2, self.V), dtype=np.complex128) if return_field else None
+        check(lib.sm_wilson_flow(self.ctx, ctypes.byref(p), series, None if U is None else _vp(U[0]),
+                                 None if U is None else _vp(U[1])))
+        t = np.arange(points, dtype=np.float64) * (p.meas_every * p.eps)
+        s = FlowSeries(t, *_topo_arrays(series, (points,)))
+        return (s, U) if return_field else s
+
     def ensemble(self, R):
         """An Ensemble of R independent HMC chains on this lattice, evolved in
         lockstep with one launch per step for all of them (sm_ens_create)."""
@@ -378,6 +434,30 @@ class Ensemble:
                                          int(CG.max_iter if max_iter is None else max_iter), mode, n, sx, st, _vp(C),
                                          res))
         return C, [list(res[r * 2 * n:(r + 1) * 2 * n]) for r in range(self.R)]
+
+    def topology(self):
+        """Topology(action, q_geo, q_sin) of every replica's current field, arrays
+        of R (sm_ens_topology): one launch for all replicas, bitwise
+        Lattice.topology on a lone context holding that field."""
+        out = (Topo * self.R)()
+        check(lib.sm_ens_topology(self.ens, out))
+        return Topology(*_topo_arrays(out, (self.R,)))
+
+    def wilson_flow(self, eps, nsteps, meas_every=1, return_field=False):
+        """Wilson flow of every replica's field, one launch per stage for all of
+        them (sm_ens_wilson_flow; the replicas' fields are not changed, and a
+        trajectory after it is the trajectory without it). Returns
+        FlowSeries(t, action, q_geo, q_sin), arrays of shape (R, points) with
+        points = 1 + nsteps // meas_every; with return_field also the flowed
+        fields, complex128 of shape (R, 2, V). Replica r's row is bitwise
+        Lattice.wilson_flow on a lone context holding that field."""
+        p, points = _flow_params(eps, nsteps, meas_every)
+        series = (Topo * (self.R * points))()
+        U = np.empty((self.R, 2, self.V), dtype=np.complex128) if return_field else None
+        check(lib.sm_ens_wilson_flow(self.ens, ctypes.byref(p), series, None if U is None else _vp(U)))
+        t = np.broadcast_to(np.arange(points, dtype=np.float64) * (p.meas_every * p.eps), (self.R, points)).copy()
+        s = FlowSeries(t, *_topo_arrays(series, (self.R, points)))
+        return (s, U) if return_field else s
 
     def trajectory(self, params, traj):
         """One HMC update of every replica (sm_ens_hmc_trajectory): params is a

@@ -46,6 +46,14 @@ class HMCResult(ctypes.Structure):
                 ("cg_failures", ctypes.c_int)]
 
 
+class Topo(ctypes.Structure):
+    _fields_ = [("action", ctypes.c_double), ("q_geo", ctypes.c_double), ("q_sin", ctypes.c_double)]
+
+
+class FlowParams(ctypes.Structure):
+    _fields_ = [("eps", ctypes.c_double), ("nsteps", ctypes.c_int), ("meas_every", ctypes.c_int)]
+
+
 class CGMixedInfo(ctypes.Structure):
     _fields_ = [("used", ctypes.c_int), ("inner_iterations", ctypes.c_int), ("reliable_updates", ctypes.c_int),
                 ("fp64_iterations", ctypes.c_int), ("fell_back", ctypes.c_int), ("true_residual", ctypes.c_double)]
@@ -168,6 +176,12 @@ def _load():
         "sm_ens_hmc_trajectory": ([vp, ctypes.POINTER(HMCParams), u64, ctypes.POINTER(HMCResult)], ci),
         "sm_ens_hmc_run": ([vp, ctypes.POINTER(HMCParams), ci, u64, ci, ci, ci, ctypes.c_char_p,
                             ctypes.POINTER(HMCSummary), vp, vp], ci),
+        # topological charge and Wilson flow
+        "sm_flow_points": ([ctypes.POINTER(FlowParams)], ci),
+        "sm_topology": ([vp, ctypes.POINTER(Topo)], ci),
+        "sm_wilson_flow": ([vp, ctypes.POINTER(FlowParams), ctypes.POINTER(Topo), vp, vp], ci),
+        "sm_ens_topology": ([vp, ctypes.POINTER(Topo)], ci),
+        "sm_ens_wilson_flow": ([vp, ctypes.POINTER(FlowParams), ctypes.POINTER(Topo), vp], ci),
     }
     for name, (args, res) in sig.items():
         if ab_override and not hasattr(lib, name):

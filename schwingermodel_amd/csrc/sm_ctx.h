@@ -284,6 +284,14 @@ struct sm_ctx {
     int pn_K = 0;
     double2 *pn_buf = nullptr;      // pn_K x 7V complex
 
+    // topological charge and Wilson flow (sm_flow.cpp). sm_topology works in
+    // partials / sums; a flow (one shard) in two field buffers and one
+    // accumulator of its own, allocated at the first flow, and a device series.
+    double2 *fl_W[2] = {};          // 2V complex each: a stage reads one (or U) and writes the other
+    double *fl_A = nullptr;         // 2V doubles
+    double *fl_series = nullptr;    // 3 doubles per measured point, regrown for a longer series
+    long fl_points = 0;
+
     double2 *field(int i) { return fields[i]; }
 };
 
@@ -482,6 +490,7 @@ int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src,
 int pion_correlator_eo(sm_ctx *c, double m0, double tol, int max_iter, int nsrc, const int *sx, const int *st,
                        double *C, sm_cg_result *res);
 void pion_free(sm_ctx *c);
+void flow_free(sm_ctx *c);  // the Wilson flow's buffers (sm_flow.cpp)
 // The mixed-precision batched solve on the context's gauge field (sm_cgbatchmp.cpp):
 // K columns of phi -> x on the device, c->bt_info[b] = column b's report.
 int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,

@@ -28,6 +28,9 @@ struct sm_ens {
     // pion correlator (sm_pion.cpp), from the first measurement on
     int *pn_src = nullptr;                                  // 2 x kBatchMax / 2 source coordinates
     double *pn_C = nullptr;                                 // R x kBatchMax / 2 x Wt
+    // topological charge and Wilson flow (sm_flow.cpp): the series on the device, regrown for a longer one
+    double *fl_series = nullptr;                            // R x fl_points x 3
+    long fl_points = 0;
 };
 
 namespace sm_host {

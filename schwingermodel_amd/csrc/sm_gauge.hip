@@ -14,36 +14,13 @@
 // link update); one shard wraps periodically in place.
 #include "sm_device.h"
 #include "sm_fields.h"
-
-#include <float.h>
+#include "sm_gauge_site.h"
 
 namespace sm {
 
-struct GArgs {
-    const double2 *U;    // 2V: plane 0 U_t, plane 1 U_x
-    const double2 *fU;   // 2-deep U faces (nshard > 1)
-    long V;
-    int Nx, Wt, nshard;
-};
-
-// U_plane(x, t = c) for c in [-1, Wt]; x already in [0, Nx).
-__device__ __forceinline__ double2 ulink(const GArgs &a, int p, int x, int c) {
-    if (c >= 0 && c < a.Wt) return a.U[(long)x * a.Wt + c + p * a.V];
-    if (a.nshard == 1) return a.U[(long)x * a.Wt + (c < 0 ? c + a.Wt : c - a.Wt) + p * a.V];
-    const int fc = c < 0 ? c + 2 : c - a.Wt + 2;  // face slot of columns -2,-1,Wt,Wt+1
-    return a.fU[((long)fc * 2 + p) * a.Nx + x];
-}
-
-// ---- plaquette: U_01(n) = U_0(n) U_1(n+0) U*_0(n+1) U*_1(n) ----------------
-// src/gauge_conf.cpp:45-49; sums as MeasureSp_HMC (:430-440) and
-// Compute_gaugeAction (:444-453): partial.x = sum Re U_01,
-// partial.y = sum beta Re(1 - U_01).
-__device__ __forceinline__ double2 plaquette_site(const GArgs &a, long n) {
-    const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
-    const int xp = x + 1 == a.Nx ? 0 : x + 1;
-    return cmul(cmul(cmul(a.U[n], ulink(a, 1, x, t + 1)), cconj(ulink(a, 0, xp, t))), cconj(a.U[n + a.V]));
-}
-
+// ---- plaquette sums (U_01(n) = plaquette_site, sm_gauge_site.h) as
+// MeasureSp_HMC (src/gauge_conf.cpp:430-440) and Compute_gaugeAction
+// (:444-453): partial.x = sum Re U_01, partial.y = sum beta Re(1 - U_01).
 __global__ void __launch_bounds__(256) plaquette_kernel(GArgs a, double beta, double2 *field,
                                                         double2 *partials) {
     __shared__ double2 sh[4];
@@ -59,18 +36,12 @@ __global__ void __launch_bounds__(256) plaquette_kernel(GArgs a, double beta, do
 }
 
 // ---- staples and gauge force (src/gauge_conf.cpp:95-125; src/hmc.cpp:31-40) --
-//   S_0(n) = U_1(n) U_0(n+1) U*_1(n+0) + U*_1(n-1) U_0(n-1) U_1(n-1+0)
-//   S_1(n) = U_0(n) U_1(n+0) U*_0(n+1) + U*_0(n-0) U_1(n-0) U_0(n+1-0)
+//   S_mu(n): staples_at (sm_gauge_site.h)
 //   F_mu(n) += -beta Im(U_mu(n) conj(S_mu(n)))
-// (0 = t direction, 1 = x direction; "n+1" is x+1, "n+0" is t+1.)
 __device__ __forceinline__ void staple_site(const GArgs &a, long n, double beta, double *F, double2 *staples) {
-    const int x = (int)(n / a.Wt), t = (int)(n - (long)x * a.Wt);
-    const int xp = x + 1 == a.Nx ? 0 : x + 1, xm = x == 0 ? a.Nx - 1 : x - 1;
     const double2 u0 = a.U[n], u1 = a.U[n + a.V];
-    const double2 S0 = cadd(cmul(cmul(u1, ulink(a, 0, xp, t)), cconj(ulink(a, 1, x, t + 1))),
-                            cmul(cmul(cconj(ulink(a, 1, xm, t)), ulink(a, 0, xm, t)), ulink(a, 1, xm, t + 1)));
-    const double2 S1 = cadd(cmul(cmul(u0, ulink(a, 1, x, t + 1)), cconj(ulink(a, 0, xp, t))),
-                            cmul(cmul(cconj(ulink(a, 0, x, t - 1)), ulink(a, 1, x, t - 1)), ulink(a, 0, xp, t - 1)));
+    double2 S0, S1;
+    staples_at(a, n, u0, u1, S0, S1);
     if (staples) {
         staples[n] = S0;
         staples[n + a.V] = S1;
@@ -89,9 +60,8 @@ __global__ void __launch_bounds__(256) staple_force_kernel(GArgs a, double beta,
 
 // ---- leapfrog link / momentum update (src/hmc.cpp:63-101) --------------------
 //   do_p:  P += eps * F
-//   U *= exp(i coef P): std::exp of (+-0, coef*P) is glibc cexp = (cos y, sin y)
-//          for |y| > DBL_MIN and (1, y) below (s_cexp_template.c); then the
-//          plain complex product. coef = eps (full step) or 0.5*eps (half).
+//   U *= exp(i coef P): cexp_i (sm_gauge_site.h), then the plain complex
+//          product. coef = eps (full step) or 0.5*eps (half).
 __device__ __forceinline__ void md_update_link(long i, double2 *U, double *P, const double *F, double eps, int do_p,
                                                double coef) {
     double p = P[i];
@@ -99,15 +69,7 @@ __device__ __forceinline__ void md_update_link(long i, double2 *U, double *P, co
         p += eps * F[i];
         P[i] = p;
     }
-    const double y = coef * p;
-    double s, c;
-    if (fabs(y) > DBL_MIN) {
-        sincos(y, &s, &c);
-    } else {
-        s = y;
-        c = 1.0;
-    }
-    U[i] = cmul(U[i], make_double2(c, s));
+    U[i] = cmul(U[i], cexp_i(coef * p));
 }
 
 __global__ void __launch_bounds__(256) md_update_kernel(long n2, double2 *U, double *P, const double *F,
@@ -267,16 +229,6 @@ __global__ void __launch_bounds__(256) ens_sums_kernel(int nparts, const double2
 
 // ---- launchers -----------------------------------------------------------------
 namespace {
-GArgs gargs(const Geometry &g, int nshard, const double2 *U, const double2 *fU) {
-    GArgs a;
-    a.U = U;
-    a.fU = fU;
-    a.V = g.V;
-    a.Nx = g.Nx;
-    a.Wt = g.Wt;
-    a.nshard = nshard;
-    return a;
-}
 DrawArgs dargs(const Geometry &g, uint64_t seed) {
     DrawArgs a;
     a.seed = seed;
@@ -286,10 +238,6 @@ DrawArgs dargs(const Geometry &g, uint64_t seed) {
     a.t0 = g.t0;
     a.Ntg = g.Ntg;
     return a;
-}
-unsigned grid_for(long n) {
-    long nb = (n + 255) / 256;
-    return (unsigned)(nb > 4096 ? 4096 : (nb < 1 ? 1 : nb));
 }
 }  // namespace
 

@@ -366,6 +366,26 @@ void launch_ens_sums(hipStream_t s, const Geometry &g, int nrows, const double2 
 void launch_ens_force(hipStream_t s, const Geometry &g, int R, const double2 *U, const double2 *l, const double2 *r,
                       double *F);
 
+// ---- topological charge and Wilson flow (sm_flow.hip; host: sm_flow.cpp) ----
+// The three sums of a field: blocks write two rows of gauge_reduce_blocks(g)
+// partials, (sum 1 - Re U_01, sum atan2(Im U_01, Re U_01)) then (sum Im U_01, 0);
+// the ensemble form writes replica r's row pair 2 r rows in. launch_topo_sums
+// sums nfields row pairs into out[i * ostride + 0, 1, 2] in launch_sum_partials'
+// order, so a replica's sums are bitwise the one-field path's.
+void launch_topo(hipStream_t s, const Geometry &g, int nshard, const double2 *U, const double2 *fU,
+                 double2 *partials);
+void launch_ens_topo(hipStream_t s, const Geometry &g, int R, const double2 *U, double2 *partials);
+void launch_topo_sums(hipStream_t s, const Geometry &g, int nfields, const double2 *partials, double *out,
+                      long ostride);
+// Stage 0, 1 or 2 of a flow step of size eps, one shard: A = ca (eps Z(Uin)) - cb A,
+// Wout = Uin exp(i rot A) with (ca, cb, rot) = (1, 0, 1/4), (8/9, 17/36, 1), (3/4, 1, 1);
+// stage 0 does not read A, stage 2 does not write it. Wout must not be Uin.
+// A: 2V doubles per field, Uin / Wout: 2V complex.
+void launch_flow_stage(hipStream_t s, const Geometry &g, int stage, double eps, const double2 *Uin, double *A,
+                       double2 *Wout);
+void launch_ens_flow_stage(hipStream_t s, const Geometry &g, int R, int stage, double eps, const double2 *Uin,
+                           double *A, double2 *Wout);
+
 // ---- even-odd checkerboard (sm_eo.hip) ----
 void launch_to_cb(hipStream_t s, const Geometry &g, const double2 *full, double2 *e, double2 *o);
 void launch_from_cb(hipStream_t s, const Geometry &g, const double2 *e, const double2 *o, double2 *full);
