@@ -70,6 +70,13 @@ void sm_fill_gauge(uint64_t seed, double sigma, int Nt_global, int x0, int nx, i
                    double *U0, double *U1);
 void sm_fill_spinor(uint64_t seed, int Nt_global, int x0, int nx, int t0, int Wt, double *p0,
                     double *p1);
+/* Noise vector k of `seed` for the stochastic quark loops (sm_quark_loops):
+ * eta_a(n) = (+-1 +- i) / sqrt(2), the two signs two bits of the counter hash
+ * keyed by (seed, k), plane a and the global site. No libm call: bitwise the
+ * values the device regenerates. The layout and the window arguments of
+ * sm_fill_spinor. */
+void sm_fill_noise(uint64_t seed, uint64_t k, int Nt_global, int x0, int nx, int t0, int Wt, double *p0,
+                   double *p1);
 
 /* 28-byte-record binary gauge configuration (src/gauge_conf.cpp:378-423
  * SaveConf / :495-546 readBinary): per site x-major, t-minor, mu = 0,1:
@@ -818,6 +825,68 @@ int sm_wilson_flow(sm_ctx *ctx, const sm_flow_params *p, sm_topo *series /* poin
 int sm_ens_topology(sm_ens *e, sm_topo *out /* R */);
 int sm_ens_wilson_flow(sm_ens *e, const sm_flow_params *p, sm_topo *series /* R * points, replica-major */,
                        double *U_out /* nullable, host: R x (plane 0, plane 1) of V complex */);
+
+/* ==== stochastic quark loops: chiral condensate and eta correlator ==========
+ * Traces of D^-1 per time slice, estimated with noise vectors, for a context's
+ * field and for every replica of an ensemble
+ * (schwingermodel_amd/csrc/sm_loops.cpp, sm_loops.hip). Not in the reference.
+ * Noise vector k of `seed` is complex Z2 x Z2 noise, eta_k,a(n) = (+-1 +- i) /
+ * sqrt(2), drawn on the device and bitwise what sm_fill_noise(seed, k, ...)
+ * writes on the host. With psi_k = D^-1 eta_k and gamma5 = diag(1, -1) (the
+ * convention behind the pion's gamma5-hermiticity), per vector and time slice
+ *   S_k(t) = sum_x sum_a conj(eta_k,a(x,t)) psi_k,a(x,t)   -> E_k S_k(t) = Tr_t D^-1
+ *   P_k(t) = sum_x (conj(eta_k,0) psi_k,0 - conj(eta_k,1) psi_k,1)(x,t)
+ *                                                  -> E_k P_k(t) = Tr_t gamma5 D^-1
+ * so that the chiral condensate is (Nf / V) Re sum_t mean_k S_k(t), and the
+ * disconnected piece of the flavour-singlet pseudoscalar comes from products
+ * P_k(t) P_k'(t + dt) of different vectors (schwingermodel_amd/loops.py has
+ * the estimators). t is the absolute time coordinate.
+ * Layout: loops[((k*Nt) + t)*4 + c], c = Re S, Im S, Re P, Im P, on the host;
+ * res[k] (nullable) reports vector k's solve. The ensemble:
+ * loops[(((r*nnoise) + k)*Nt + t)*4 + c], res[r*nnoise + k] (nullable), replica
+ * r with mass m0[r] and seed seed[r].
+ * solver 0: y = (D D^dag)^-1 eta by the batched CG (sm_cg_batch's solver: one
+ * launch per iteration for all columns), then ONE fused launch that forms psi =
+ * D^dag y at each site in registers, regenerates eta from its counter and adds
+ * up the slices: it reads y and the links (32 + 32 B per site and column, the
+ * links from cache after a shared field's first column) and stores neither psi
+ * nor eta. The context solves its nnoise vectors in chunks of at most
+ * sm_cg_batch_max() columns (nnoise itself is not capped) and follows
+ * sm_cg_batch_precision exactly as sm_pion_correlator does; the ensemble makes
+ * one batched solve of R columns per vector, column r on replica r's links and
+ * mass, and one contraction launch for all replicas, always fp64.
+ * solver 1: the even-odd system of sm_pion_solver = 1 on the noise (phihat_e,
+ * the batched even-odd solve, S_e, S_o, back to the full layout: the same code
+ * the pion correlator runs), then the contraction on the stored psi. Always
+ * fp64; res reports the even-odd solves. Needs even Nx and Nt: SM_ERR_ARG
+ * naming the checkerboard otherwise, and solver 0 keeps working.
+ * Vector k's loops and res[k] depend on the field, m0, tol, max_iter, seed and
+ * k only: not on nnoise or the chunking, and they are bitwise the same on
+ * every call (fixed summation order, no atomics). Replica r's loops and res
+ * are bitwise sm_quark_loops' on a lone context holding that field with m0[r]
+ * and seed[r], with either solver: the same at R = 1, at any position and next
+ * to any neighbours.
+ * These are measurements: the context's gauge field, the ensemble's fields and
+ * the HMC state are not written; a trajectory, sm_cg_batch or
+ * sm_pion_correlator after a call is bitwise the one without it.
+ * Memory. The context works in sm_cg_batch's workspace and staging (solver 1:
+ * sm_pion_solver = 1's), for min(nnoise, sm_cg_batch_max()) columns; the
+ * ensemble in its chi, phi, x and solver workspaces (solver 1: its even-odd
+ * fields), free between trajectories. New memory: 32 B per vector and time
+ * slice on the device (per replica for the ensemble) and 1 KiB of seeds.
+ * SM_ERR_ARG for a null context, ensemble, loops (ensemble: m0, seed),
+ * nnoise < 1, solver not 0 or 1, max_iter < 0 and on sharded, host-staged,
+ * loopback and peer contexts; SM_ERR_STATE before a gauge upload or while some
+ * replica has no field; SM_ERR_HIP naming the bytes asked for when an
+ * allocation fails, after which the context or ensemble stays usable. Both
+ * calls are synchronous.
+ * Not in this version: dilution, t-shards, a loops column in sm_hmc_run /
+ * sm_ens_hmc_run. */
+int sm_quark_loops(sm_ctx *ctx, double m0, double tol, int max_iter, int solver, int nnoise, uint64_t seed,
+                   double *loops /* nnoise*Nt*4, host */, sm_cg_result *res /* nnoise, nullable */);
+int sm_ens_quark_loops(sm_ens *e, const double *m0 /* R */, double tol, int max_iter, int solver, int nnoise,
+                       const uint64_t *seed /* R */, double *loops /* R*nnoise*Nt*4, host */,
+                       sm_cg_result *res /* R*nnoise, nullable */);
 
 /* Gather the sharded gauge field to shard 0 (SaveConf's MPI_Gatherv,
  * src/gauge_conf.cpp:378-396): U0/U1 on shard 0 receive the global

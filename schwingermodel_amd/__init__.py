@@ -77,6 +77,27 @@ def _topo_arrays(buf, shape):
     return tuple(np.array(a[..., i]) for i in range(3))
 
 
+def _loops_args(who, solver, nnoise, seeds, R):
+    """(solver mode, nnoise, seeds as a uint64 array of R) of a quark_loops call,
+    checked as sm_quark_loops / sm_ens_quark_loops check them."""
+    mode = Lattice.PION_SOLVERS.get(solver, solver) if isinstance(solver, str) else solver
+    if not isinstance(mode, int) or isinstance(mode, bool) or mode not in (0, 1):
+        raise ValueError(f"{who}: solver {solver!r}: 'plain' or 'even_odd'")
+    if isinstance(nnoise, bool) or not isinstance(nnoise, (int, np.integer)):
+        raise TypeError(f"{who}: nnoise = {nnoise!r}, expected an integer")
+    if nnoise < 1 or nnoise > 2**31 - 1:
+        raise ValueError(f"{who}: nnoise = {nnoise!r}, expected an integer >= 1")
+    seeds = list(seeds)
+    if len(seeds) != R:
+        raise ValueError(f"{who}: {len(seeds)} seeds for {R} replicas")
+    for s in seeds:
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)):
+            raise TypeError(f"{who}: seed = {s!r}, expected an integer")
+        if not 0 <= s < 2**64:
+            raise ValueError(f"{who}: seed = {s!r} outside 0..2^64 - 1")
+    return mode, int(nnoise), np.array([int(s) for s in seeds], dtype=np.uint64)
+
+
 class spinor:
     """Reference spinor (include/variables.h:54): two complex<double> arrays."""
 
@@ -282,6 +303,24 @@ class Lattice:
         check(lib.sm_pion_solver(self.ctx, m, ctypes.byref(cur)))
         return "even_odd" if cur.value == 1 else "plain"
 
+    def quark_loops(self, m0, nnoise, seed, solver="plain", tol=None, max_iter=None):
+        """Stochastic quark loops on the context's current gauge field
+        (sm_quark_loops; no implicit upload): nnoise Z2 x Z2 noise vectors of
+        `seed`, vector k bitwise sm_fill_noise(seed, k, ...). Returns (loops,
+        results): loops complex of shape (nnoise, Nt, 2), [k, t, 0] = S_k(t) =
+        sum_x eta^dag D^-1 eta and [k, t, 1] = P_k(t) = sum_x eta^dag gamma5
+        D^-1 eta at absolute time t; results[k] the solve of vector k. solver:
+        "plain" (D D^dag, following cg_batch_precision) or "even_odd" (always
+        fp64, even Nx and Nt). The estimators are in schwingermodel_amd.loops."""
+        mode, n, sd = _loops_args("quark_loops", solver, nnoise, [seed], 1)
+        out = np.zeros((n, self.Wt, 4))
+        res = (CGResult * n)()
+        check(lib.sm_quark_loops(self.ctx, float(m0), float(CG.tol if tol is None else tol),
+                                 int(CG.max_iter if max_iter is None else max_iter), mode, n,
+                                 ctypes.c_uint64(int(sd[0])), _vp(out), res))
+        self._batch_K = (n - 1) % lib.sm_cg_batch_max() + 1  # the last chunk's columns
+        return out.view(np.complex128), list(res)
+
     def topology(self):
         """Topology(action, q_geo, q_sin) of the context's current gauge field
         (sm_topology; 0-d float arrays): sum (1 - Re U_01), the geometric charge
@@ -434,6 +473,25 @@ class Ensemble:
                                          int(CG.max_iter if max_iter is None else max_iter), mode, n, sx, st, _vp(C),
                                          res))
         return C, [list(res[r * 2 * n:(r + 1) * 2 * n]) for r in range(self.R)]
+
+    def quark_loops(self, m0s, nnoise, seeds, solver="plain", tol=None, max_iter=None):
+        """Stochastic quark loops of every replica on its current field with its
+        own mass m0s[r] and noise seed seeds[r] (sm_ens_quark_loops): for each
+        vector one batched solve of R columns and one contraction launch for
+        all replicas. Returns (loops, results): loops complex of shape (R,
+        nnoise, Nt, 2) as Lattice.quark_loops, results[r][k] the solve of
+        replica r's vector k. Replica r's row is bitwise Lattice.quark_loops on
+        a lone context holding that field, with either solver. Always fp64."""
+        m = np.ascontiguousarray(m0s, dtype=np.float64)
+        if m.shape != (self.R,):
+            raise ValueError(f"ensemble: {m.size} masses for {self.R} replicas")
+        mode, n, sd = _loops_args("ensemble quark_loops", solver, nnoise, seeds, self.R)
+        out = np.zeros((self.R, n, self.lattice.Wt, 4))
+        res = (CGResult * (self.R * n))()
+        check(lib.sm_ens_quark_loops(self.ens, _vp(m), float(CG.tol if tol is None else tol),
+                                     int(CG.max_iter if max_iter is None else max_iter), mode, n, _vp(sd), _vp(out),
+                                     res))
+        return out.view(np.complex128), [list(res[r * n:(r + 1) * n]) for r in range(self.R)]
 
     def topology(self):
         """Topology(action, q_geo, q_sin) of every replica's current field, arrays

@@ -76,6 +76,7 @@ def _load():
         "sm_shard_plan": ([ci, ci, ci, ctypes.POINTER(ci), ctypes.POINTER(ci)], ci),
         "sm_fill_gauge": ([u64, cd, ci, ci, ci, ci, ci, vp, vp], None),
         "sm_fill_spinor": ([u64, ci, ci, ci, ci, ci, vp, vp], None),
+        "sm_fill_noise": ([u64, u64, ci, ci, ci, ci, ci, vp, vp], None),
         "sm_conf_write": ([ctypes.c_char_p, ci, ci, vp, vp], ci),
         "sm_conf_read": ([ctypes.c_char_p, ci, ci, vp, vp], ci),
         "sm_comm_unique_id": ([vp, ci], ci),
@@ -182,6 +183,9 @@ def _load():
         "sm_wilson_flow": ([vp, ctypes.POINTER(FlowParams), ctypes.POINTER(Topo), vp, vp], ci),
         "sm_ens_topology": ([vp, ctypes.POINTER(Topo)], ci),
         "sm_ens_wilson_flow": ([vp, ctypes.POINTER(FlowParams), ctypes.POINTER(Topo), vp], ci),
+        # stochastic quark loops
+        "sm_quark_loops": ([vp, cd, cd, ci, ci, ci, u64, vp, ctypes.POINTER(CGResult)], ci),
+        "sm_ens_quark_loops": ([vp, vp, cd, ci, ci, ci, vp, vp, ctypes.POINTER(CGResult)], ci),
     }
     for name, (args, res) in sig.items():
         if ab_override and not hasattr(lib, name):

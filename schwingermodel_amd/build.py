@@ -16,9 +16,9 @@ LIB = os.path.join(HERE, "libsm_hip.so")
 SOURCES = ["sm_kernels.hip", "sm_cgfused.hip", "sm_cgra.hip", "sm_cgsp.hip", "sm_eotd.hip", "sm_gauge.hip", "sm_eo.hip", "sm_peer.hip", "sm_capi.cpp", "sm_comm.cpp", "sm_place.cpp", "sm_conf.cpp", "sm_md.cpp", "sm_hmc.cpp", "sm_cgmp.cpp",
            "sm_eo.cpp", "sm_eosp.hip", "sm_eomp.cpp", "sm_cgbatch.hip", "sm_cgbatch.cpp", "sm_ens.cpp",
            "sm_cgbatchsp.hip", "sm_cgbatchmp.cpp", "sm_eobatch.hip", "sm_eobatch.cpp", "sm_pion.hip", "sm_pion.cpp",
-           "sm_flow.hip", "sm_flow.cpp"]
+           "sm_flow.hip", "sm_flow.cpp", "sm_loops.hip", "sm_loops.cpp"]
 HEADERS = ["sm_internal.h", "sm_fields.h", "sm_device.h", "sm_ctx.h", "sm_linkcode.h", "sm_peer.h", "sm_ens_host.h", "sm_cg_host.h", "sm_ens.h",
-           "sm_pion_host.h", "sm_gauge_site.h"]
+           "sm_pion_host.h", "sm_gauge_site.h", "sm_loops_host.h"]
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")

@@ -640,6 +640,7 @@ int sm_destroy(sm_ctx *c) {
     eo_batch_free(c);
     pion_free(c);
     flow_free(c);
+    loops_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
                    c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};

@@ -105,7 +105,7 @@ static int batch_ready(sm_ctx *c, int K) {
 }
 
 // Device staging for the host-pointer entry and the correlator: phi and x, K columns.
-static int staging_ready(sm_ctx *c, int K) {
+int batch_staging_ready(sm_ctx *c, int K) {
     if (c->bt_pion_K >= K) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
     free_dev(c->bt_phi);
@@ -147,7 +147,7 @@ int cg_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, doubl
 
 // Every batched solve of the entry points below: this file's fp64 solver on the
 // context's workspace, or the mixed-precision one (sm_cg_batch_precision).
-static int batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
+int batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
                        sm_cg_result *res) {
     c->bt_info.assign((size_t)K, sm_cg_mixed_info{});
     if (c->bt_precision == 1) return cg_batch_mixed(c, K, phi, x, m0, tol, max_iter, res);
@@ -180,7 +180,7 @@ int sm_cg_batch(sm_ctx *c, int K, const double *phi, double *x, double m0, doubl
     if (max_iter < 0) return fail(SM_ERR_ARG, "batched CG: max_iter < 0");
     TRY(check_ready(c));
     HIP_TRY(hipSetDevice(c->device));
-    TRY(staging_ready(c, K));
+    TRY(batch_staging_ready(c, K));
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
     HIP_TRY(hipMemcpyAsync(c->bt_phi, phi, fb, hipMemcpyHostToDevice, c->stream));
     TRY(batch_solve(c, K, c->bt_phi, c->bt_x, m0, tol, max_iter, res));
@@ -208,7 +208,7 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
                     "an odd periodic lattice has no checkerboard", c->g.Nx, c->g.Wt);
     TRY(check_ready(c));
     HIP_TRY(hipSetDevice(c->device));
-    if (!eo) TRY(staging_ready(c, K));
+    if (!eo) TRY(batch_staging_ready(c, K));
     if (!c->bt_src) TRY(alloc_dev((void **)&c->bt_src, sizeof(int) * kBatchMax, kBatchWho, "source coordinates"));
     if (!c->bt_C) TRY(alloc_dev((void **)&c->bt_C, sizeof(double) * (kBatchMax / 2) * (size_t)c->g.Wt, kBatchWho,
                                    "correlator"));

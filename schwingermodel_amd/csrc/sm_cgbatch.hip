@@ -317,18 +317,7 @@ __global__ void __launch_bounds__(64) batch_flush_kernel(int P, const double2 *p
 }
 
 // ---- the start of a solve: x = phi, r_0 = phi - D D^dag phi, d_0 = r_0 -------
-// One thread per site, periodic neighbours (one shard).
-template <int DAG>
-__device__ __forceinline__ void site_apply(const double2 *in, const double2 *U, int Nx, int Wt, long V, double mass,
-                                           int x, int t, double2 &o0, double2 &o1) {
-    const int tp = t + 1 == Wt ? 0 : t + 1, tm = t == 0 ? Wt - 1 : t - 1;
-    const int xp = x + 1 == Nx ? 0 : x + 1, xm = x == 0 ? Nx - 1 : x - 1;
-    const long n = (long)x * Wt + t, nt = (long)x * Wt + tp, ntm = (long)x * Wt + tm;
-    const long nx = (long)xp * Wt + t, nxm = (long)xm * Wt + t;
-    const double sr0 = t == Wt - 1 ? -1.0 : 1.0, sl0 = t == 0 ? -1.0 : 1.0;
-    dirac_site<DAG>(mass, sr0, sl0, in[n], in[n + V], in[nt], in[nt + V], in[nx], in[nx + V], in[ntm], in[ntm + V],
-                    in[nxm], in[nxm + V], U[n], U[n + V], U[ntm], U[nxm + V], o0, o1);
-}
+// One thread per site, periodic neighbours (one shard): site_apply, sm_device.h.
 
 // out_b = D in_b (DAG = 0) or D^dag in_b (1) on column b's links and mass;
 // grid NBA x K: block (q, b) takes sites q*256 + tid of column b

@@ -23,6 +23,11 @@ void sm_fill_spinor(uint64_t seed, int Nt_global, int x0, int nx, int t0, int Wt
     sm_fields_fill_spinor(seed, Nt_global, x0, nx, t0, Wt, p0, p1);
 }
 
+void sm_fill_noise(uint64_t seed, uint64_t k, int Nt_global, int x0, int nx, int t0, int Wt, double *p0,
+                   double *p1) {
+    sm_fields_fill_noise(seed, k, Nt_global, x0, nx, t0, Wt, p0, p1);
+}
+
 int sm_conf_write(const char *path, int Nx, int Nt, const double *U0, const double *U1) {
     FILE *f = fopen(path, "wb");
     if (!f) return fail(SM_ERR_ARG, "cannot open %s", path);

@@ -292,6 +292,12 @@ struct sm_ctx {
     double *fl_series = nullptr;    // 3 doubles per measured point, regrown for a longer series
     long fl_points = 0;
 
+    // stochastic quark loops (sm_loops.cpp), from the first call on: the columns' (seed, k) and the
+    // loops of lp_cols columns on the device. Solves and fields are the batched CG's / the pion's above.
+    uint64_t *lp_sk = nullptr;      // 2 x kBatchMax: seeds, then vector numbers
+    double *lp_out = nullptr;       // lp_cols x Wt x 4
+    size_t lp_cols = 0;
+
     double2 *field(int i) { return fields[i]; }
 };
 
@@ -475,6 +481,12 @@ int cg_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, doubl
 int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res);
 void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's (sm_cgbatch.cpp)
+// (sm_cgbatch.cpp) the context's device staging bt_phi / bt_x for K columns; and every batched solve
+// of its entry points: K columns of phi -> x on the context's field with m0, fp64 on c->bt or the
+// mixed solver (sm_cg_batch_precision), c->bt_info = the columns' reports
+int batch_staging_ready(sm_ctx *c, int K);
+int batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
+                sm_cg_result *res);
 void eo_batch_free(sm_ctx *c);
 // The context's even-odd batch workspace for K columns and its checkerboard link buffer (sm_eobatch.cpp)
 int eob_ready(sm_ctx *c, int K);
@@ -486,11 +498,19 @@ int eob_ready(sm_ctx *c, int K);
 // fields of K x V complex; S: K full-layout columns.
 int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src, double2 *eh, const EoBatchLinks &l,
                         double tol, int max_iter, sm_cg_result *res, double2 *S);
+// The same from sources already in eh's first two fields (phi_e, phi_o): what
+// pion_eo_propagators runs after writing its point sources, and the quark
+// loops (sm_loops.cpp) after their noise.
+int eo_propagators(sm_ctx *c, const BatchWs &w, int K, double2 *eh, const EoBatchLinks &l, double tol, int max_iter,
+                   sm_cg_result *res, double2 *S);
+// The context's even-odd batch workspace and pn_buf for K columns
+int pion_eo_ready(sm_ctx *c, int K);
 // sm_pion_correlator's body in mode 1 (arguments checked by the caller; sx / st: device)
 int pion_correlator_eo(sm_ctx *c, double m0, double tol, int max_iter, int nsrc, const int *sx, const int *st,
                        double *C, sm_cg_result *res);
 void pion_free(sm_ctx *c);
 void flow_free(sm_ctx *c);  // the Wilson flow's buffers (sm_flow.cpp)
+void loops_free(sm_ctx *c); // the quark loops' buffers (sm_loops.cpp)
 // The mixed-precision batched solve on the context's gauge field (sm_cgbatchmp.cpp):
 // K columns of phi -> x on the device, c->bt_info[b] = column b's report.
 int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,

@@ -145,6 +145,21 @@ __device__ __forceinline__ void dirac_site(double mass, double sr0, double sl0, 
     s1 = csub(rmul(mass, p1), rmul(0.5, h1));
 }
 
+// dirac_site at site (x, t) of a one-shard field read from memory, periodic
+// neighbours: the site expression of the batched solvers' apply and start
+// kernels (sm_cgbatch.hip) and of the quark loops' contraction (sm_loops.hip).
+template <int DAG>
+__device__ __forceinline__ void site_apply(const double2 *in, const double2 *U, int Nx, int Wt, long V, double mass,
+                                           int x, int t, double2 &o0, double2 &o1) {
+    const int tp = t + 1 == Wt ? 0 : t + 1, tm = t == 0 ? Wt - 1 : t - 1;
+    const int xp = x + 1 == Nx ? 0 : x + 1, xm = x == 0 ? Nx - 1 : x - 1;
+    const long n = (long)x * Wt + t, nt = (long)x * Wt + tp, ntm = (long)x * Wt + tm;
+    const long nx = (long)xp * Wt + t, nxm = (long)xm * Wt + t;
+    const double sr0 = t == Wt - 1 ? -1.0 : 1.0, sl0 = t == 0 ? -1.0 : 1.0;
+    dirac_site<DAG>(mass, sr0, sl0, in[n], in[n + V], in[nt], in[nt + V], in[nx], in[nx + V], in[ntm], in[ntm + V],
+                    in[nxm], in[nxm + V], U[n], U[n + V], U[ntm], U[nxm + V], o0, o1);
+}
+
 // Complex products of the CG passes built with FOLD = 2 (sm_cgra.hip,
 // sm_eotd.hip): fused multiply-adds, one rounding per component instead of
 // two or three; FOLD <= 1 keeps GCC's separately rounded expansion.

@@ -93,7 +93,7 @@ struct HTerms {
 
 void ens_free(sm_ens *e) {
     void *dev[] = {e->U, e->Ubak, e->chi, e->phi, e->x,   e->P,  e->F,
-                   e->par, e->massv, e->part, e->sums, e->Ucb, e->eh, e->pn_src, e->pn_C, e->fl_series};
+                   e->par, e->massv, e->part, e->sums, e->Ucb, e->eh, e->pn_src, e->pn_C, e->fl_series, e->lp_sk, e->lp_out};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     void *host[] = {e->h_par, e->h_mass, e->h_sums};

@@ -31,6 +31,10 @@ struct sm_ens {
     // topological charge and Wilson flow (sm_flow.cpp): the series on the device, regrown for a longer one
     double *fl_series = nullptr;                            // R x fl_points x 3
     long fl_points = 0;
+    // stochastic quark loops (sm_loops.cpp), from the first measurement on
+    uint64_t *lp_sk = nullptr;                              // 2 x kBatchMax: the replicas' seeds, then the vector number
+    double *lp_out = nullptr;                               // lp_cols x Wt x 4, lp_cols >= R x nnoise
+    size_t lp_cols = 0;
 };
 
 namespace sm_host {

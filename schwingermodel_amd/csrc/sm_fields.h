@@ -21,6 +21,11 @@
  * There log/sincos are the device math library's, which may differ from
  * glibc in the last bit: device-drawn fields are the same distribution, not
  * bit-identical to host-drawn ones.
+ *
+ *   noise   eta_a(n) = (+-1 +- i) / sqrt(2): complex Z2 x Z2 noise for the
+ *           stochastic quark loops (sm_loops.hip). Two bits of the counter
+ *           hash choose the signs and no libm call is involved, so host and
+ *           device values ARE bitwise equal.
  */
 #ifndef SM_FIELDS_H
 #define SM_FIELDS_H
@@ -71,9 +76,29 @@ SM_FIELDS_HD static inline uint64_t sm_traj_seed(uint64_t seed, uint64_t traj) {
 
 /* Stream ids: gauge theta 0/1 (Gaussian pairs) and 16/17 (hot); spinor
  * planes 4/5; HMC momenta 6 (one Box-Muller pair = both links of a site);
- * Metropolis uniform 7 (uniform stream 7, index 0). */
+ * Metropolis uniform 7 (uniform stream 7, index 0); noise planes 20/21 (hash
+ * streams, free as uniform streams and as Gaussian pairs alike). */
 #define SM_STREAM_MOMENTA 6
 #define SM_STREAM_ACCEPT 7
+#define SM_STREAM_NOISE 20
+
+/* Z2 x Z2 noise of plane a at global site ng for the key sm_traj_seed(seed, k)
+ * of noise vector k: bit 63 of the stream's counter hash is the sign of the
+ * real part, bit 62 of the imaginary part (set = minus). Integer arithmetic
+ * and one constant only: the same bits on the host and on the device.
+ * sm_noise_stream is the part that does not depend on the site. */
+SM_FIELDS_HD static inline uint64_t sm_noise_stream(uint64_t key, int a) {
+    return sm_mix64(key ^ (0xD1B54A32D192ED03ull * ((uint64_t)(SM_STREAM_NOISE + a) + 1)));
+}
+SM_FIELDS_HD static inline void sm_noise_at(uint64_t stream, uint64_t ng, double *re, double *im) {
+    const double s = 0.70710678118654752440084436210485;
+    const uint64_t h = sm_mix64(stream + ng);
+    *re = (h >> 63) ? -s : s;
+    *im = ((h >> 62) & 1) ? -s : s;
+}
+SM_FIELDS_HD static inline void sm_noise(uint64_t key, int a, uint64_t ng, double *re, double *im) {
+    sm_noise_at(sm_noise_stream(key, a), ng, re, im);
+}
 
 /* Gauge link of global site ng: exp(i theta), theta per sigma (see top). */
 SM_FIELDS_HD static inline void sm_gauge_link(uint64_t seed, double sigma, uint64_t ng, int mu,
@@ -119,6 +144,20 @@ static inline void sm_fields_fill_spinor(uint64_t seed, int Nt_global, int x0, i
             sm_gauss2(seed, 5, ng, &g1, &g2);
             p1[2 * n] = s * g1;
             p1[2 * n + 1] = s * g2;
+        }
+    }
+}
+
+/* Noise vector k of `seed`, the layout and arguments of sm_fields_fill_spinor. */
+static inline void sm_fields_fill_noise(uint64_t seed, uint64_t k, int Nt_global, int x0, int nx, int t0,
+                                        int Wt, double *p0, double *p1) {
+    const uint64_t key = sm_traj_seed(seed, k);
+    for (int x = 0; x < nx; x++) {
+        for (int t = 0; t < Wt; t++) {
+            const uint64_t ng = (uint64_t)(x0 + x) * (uint64_t)Nt_global + (uint64_t)(t0 + t);
+            const long n = (long)x * Wt + t;
+            sm_noise(key, 0, ng, &p0[2 * n], &p0[2 * n + 1]);
+            sm_noise(key, 1, ng, &p1[2 * n], &p1[2 * n + 1]);
         }
     }
 }

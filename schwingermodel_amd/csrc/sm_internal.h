@@ -503,6 +503,21 @@ void launch_pion_eo_add(hipStream_t s, const Geometry &g, int K, int inv_mass, c
 void launch_ens_pion_slices(hipStream_t s, const Geometry &g, int R, const double2 *A, const double2 *B, double *C,
                             long cstride);
 
+// ---- stochastic quark loops (sm_loops.hip; host sm_loops.cpp) ----
+// Which noise vector each of K columns carries: column b = vector k[b] of seed[b] (device arrays).
+struct LoopNoise {
+    const uint64_t *seed, *k;
+};
+// The K noise vectors: full != null: K full-layout columns (2V complex apart); else K checkerboard
+// columns (V complex apart), e or o by the site's parity. Every site is written.
+void launch_loops_noise(hipStream_t s, const Geometry &g, int K, const LoopNoise &nz, double2 *full, double2 *e,
+                        double2 *o);
+// out[b * ostride + 4 t + c], c = Re S, Im S, Re P, Im P of column b: the slice sums of conj(eta_b) psi_b
+// with eta_b regenerated from nz and psi_b = D^dag in_b on column b's links and mass of l, formed in
+// registers (load_psi = 0), or psi_b = in_b read from memory (1; l is not read). One launch for all K.
+void launch_loops_contract(hipStream_t s, const Geometry &g, int K, int load_psi, const double2 *in,
+                           const BatchLinks &l, const LoopNoise &nz, double *out, long ostride);
+
 // ---- mixed-precision even-odd CG (sm_eosp.hip; driver sm_eomp.cpp) ----
 // Pass `pass` of a segment on float2 checkerboard fields (0: the injected
 // direction, no d store; even passes >= 2 update y): d_{j-1} in d1, d_{j-2} in

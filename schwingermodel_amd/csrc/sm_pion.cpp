@@ -19,7 +19,9 @@
 //                  X = (Dhat Dhat^dag)^-1 phihat_e,  S_e = Dhat^dag X
 //                  S_o = (1/m) phi_o + (1/2m) H_oe S_e
 //              with Dhat = m - (1/4m) H_eo H_oe; every stage one launch for all
-//              K columns. The ensemble calls it with K = R (its checkerboard
+//              K columns. Everything after the sources is eo_propagators, which
+//              the quark loops (sm_loops.cpp) run on noise sources.
+//              The ensemble calls it with K = R (its checkerboard
 //              links, rebuilt once per measurement, and five of its six
 //              half-lattice fields), the context with K = 2 nsrc on the shared
 //              links of sm_eo_cg_batch's workspace.
@@ -40,15 +42,13 @@ using namespace sm;
 
 namespace sm_host {
 
-int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src, double2 *eh, const EoBatchLinks &l,
-                        double tol, int max_iter, sm_cg_result *res, double2 *S) {
+int eo_propagators(sm_ctx *c, const BatchWs &w, int K, double2 *eh, const EoBatchLinks &l, double tol, int max_iter,
+                   sm_cg_result *res, double2 *S) {
     const Geometry &g = c->g;
     hipStream_t s = c->stream;
     const size_t hv = (size_t)K * (size_t)g.V;
     // slots: phi_e (later S_o), phi_o, phihat_e (later Dhat^dag's odd work field), X, S_e
     double2 *pe = eh, *po = eh + hv, *ph = eh + 2 * hv, *X = eh + 3 * hv, *Se = eh + 4 * hv;
-    HIP_TRY(hipMemsetAsync(pe, 0, sizeof(double2) * 2 * hv, s));
-    launch_pion_sources(s, g, K, src, nullptr, pe, po);
     launch_eob_hop(s, g, K, 0, 0, 2, po, nullptr, ph, l);  // (1/2m) H_eo phi_o
     launch_pion_eo_add(s, g, K, 0, pe, ph, l);
     HIP_TRY(hipGetLastError());
@@ -62,24 +62,37 @@ int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src,
     return SM_OK;
 }
 
+int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src, double2 *eh, const EoBatchLinks &l,
+                        double tol, int max_iter, sm_cg_result *res, double2 *S) {
+    const size_t hv = (size_t)K * (size_t)c->g.V;
+    HIP_TRY(hipMemsetAsync(eh, 0, sizeof(double2) * 2 * hv, c->stream));
+    launch_pion_sources(c->stream, c->g, K, src, nullptr, eh, eh + hv);
+    return eo_propagators(c, w, K, eh, l, tol, max_iter, res, S);
+}
+
 void pion_free(sm_ctx *c) {
     free_dev(c->pn_buf);
     c->pn_buf = nullptr;
     c->pn_K = 0;
 }
 
-int pion_correlator_eo(sm_ctx *c, double m0, double tol, int max_iter, int nsrc, const int *sx, const int *st,
-                       double *C, sm_cg_result *res) {
-    const int K = 2 * nsrc;
-    const Geometry &g = c->g;
+int pion_eo_ready(sm_ctx *c, int K) {
     TRY(eob_ready(c, K));
     if (c->pn_K < K) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         pion_free(c);
-        TRY(alloc_dev((void **)&c->pn_buf, sizeof(double2) * 7 * (size_t)g.V * (size_t)K, kEoBatchWho,
+        TRY(alloc_dev((void **)&c->pn_buf, sizeof(double2) * 7 * (size_t)c->g.V * (size_t)K, kEoBatchWho,
                       "pion correlator fields"));
         c->pn_K = K;
     }
+    return SM_OK;
+}
+
+int pion_correlator_eo(sm_ctx *c, double m0, double tol, int max_iter, int nsrc, const int *sx, const int *st,
+                       double *C, sm_cg_result *res) {
+    const int K = 2 * nsrc;
+    const Geometry &g = c->g;
+    TRY(pion_eo_ready(c, K));
     double2 *Ue = c->eob_U, *Uo = c->eob_U + g.V;
     launch_eob_to_cb(c->stream, g, 1, c->U, Ue, Uo);
     HIP_TRY(hipGetLastError());
