@@ -18,7 +18,7 @@ SOURCES = ["sm_kernels.hip", "sm_cgfused.hip", "sm_cgra.hip", "sm_cgsp.hip", "sm
            "sm_cgbatchsp.hip", "sm_cgbatchmp.cpp", "sm_eobatch.hip", "sm_eobatch.cpp", "sm_pion.hip", "sm_pion.cpp",
            "sm_flow.hip", "sm_flow.cpp", "sm_loops.hip", "sm_loops.cpp"]
 HEADERS = ["sm_internal.h", "sm_fields.h", "sm_device.h", "sm_ctx.h", "sm_linkcode.h", "sm_peer.h", "sm_ens_host.h", "sm_cg_host.h", "sm_ens.h",
-           "sm_pion_host.h", "sm_gauge_site.h", "sm_loops_host.h"]
+           "sm_pion_host.h", "sm_gauge_site.h", "sm_loops_host.h", "sm_buf.h"]
 
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")

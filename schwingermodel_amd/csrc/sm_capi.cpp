@@ -43,17 +43,25 @@ int fail(int code, const char *fmt, ...) {
     return code;
 }
 
-void free_dev(void *p) {
-    if (p) (void)hipFree(p);
-}
-
-int alloc_dev(void **p, size_t bytes, const char *who, const char *what) {
-    const hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) return SM_OK;
+// BufGroup's raw calls (sm_buf.h)
+int buf_raw_alloc(sm_ctx *c, BufKind kind, void **p, size_t bytes) {
+    const hipError_t e = kind == BufKind::pinned     ? hipHostMalloc(p, bytes)
+                         : kind == BufKind::streamed ? stream_malloc(c, p, bytes)
+                                                     : hipMalloc(p, bytes);
+    if (e == hipSuccess) return 0;
     *p = nullptr;
     (void)hipGetLastError();
-    return fail(SM_ERR_HIP, "%s: allocating %zu bytes (%s) failed: %s", who, bytes, what, hipGetErrorString(e));
+    return (int)e;
 }
+
+void buf_raw_free(sm_ctx *c, BufKind kind, void *p) {
+    if (!p) return;
+    if (kind == BufKind::pinned) (void)hipHostFree(p);
+    else if (kind == BufKind::streamed) stream_free(c, p);
+    else (void)hipFree(p);
+}
+
+const char *buf_raw_error(int err) { return hipGetErrorString((hipError_t)err); }
 
 // Neighbour sources for `in`: periodic aliases (1 GPU) or received faces.
 TFaces faces_for(sm_ctx *c, const double2 *in, const double2 *recv_lo, const double2 *recv_hi) {
@@ -160,7 +168,9 @@ int ensure_link_angles(sm_ctx *c) {
     if (c->cg_fused != 5 || c->racfg.fold < 2 || !cg_ra_ok(c)) return SM_OK;
     if (c->uang_state != 0 || !c->link_angles) return SM_OK;
     if (!c->Uang) HIP_TRY(stream_malloc(c, (void **)&c->Uang, link_code_bytes(2 * c->g.V)));
-    if (c->sharded() && !c->Uang_face) HIP_TRY(hipMalloc(&c->Uang_face, link_code_bytes(16 * (long)c->g.Nx)));
+    if (c->sharded() && c->uang_face_bufs.empty())
+        TRY(c->uang_face_bufs.add_bytes(&c->Uang_face, link_code_bytes(16 * (long)c->g.Nx), BufKind::device,
+                                        "ghost link codes"));
     // per block (links not rebuilt bitwise, links whose flag word needs 16 bits)
     int nb = launch_link_codes(c->stream, 2 * c->g.V, c->U, c->Uang, c->partials);
     if (c->sharded())
@@ -633,16 +643,7 @@ int sm_destroy(sm_ctx *c) {
         }
     stream_free(c, c->Uang);
     c->Uang = nullptr;
-    mixed_free(c, c->mp);
-    mixed_free(c, c->eomp);
-    cg_batch_free(c);
-    cg_batch_mixed_free(c);
-    eo_batch_free(c);
-    pion_free(c);
-    flow_free(c);
-    loops_free(c);
     void *dev[] = {c->U, c->ghostU, c->faces, c->faces2, c->faces4, c->partials, c->sums, c->Fbuf, c->sc,
-                   c->U_alt, c->Pmd, c->Fmd, c->eo, c->Ucb, c->eo_faces, c->eo_faces4, c->Uang_face,
                    c->tick, c->gsum};
     for (void *p : dev)
         if (p) (void)hipFree(p);
@@ -655,7 +656,7 @@ int sm_destroy(sm_ctx *c) {
         if (ev) (void)hipEventDestroy(ev);
     if (c->comm_stream && c->own_comm_stream) (void)hipStreamDestroy(c->comm_stream);
     if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-    delete c;
+    delete c;  // the workspaces' BufGroups free here: the device is current, the streams were synchronised above
     return SM_OK;
 }
 

@@ -10,7 +10,8 @@
 // The host of these steps is sm_ctx.h's batch_cg_solve, which the even-odd
 // solver (sm_eobatch.cpp) runs too: cg_batch_solve below hands it this
 // operator's two launchers. The workspace of both solvers (batch_ws_alloc,
-// batch_ws_free) is defined here.
+// batch_ws_free) is defined here; its buffers, like the staging's and the
+// correlator's, belong to BufGroups (sm_buf.h) that sm_ctx holds.
 //
 // One-shard contexts only. fp64 unless sm_cg_batch_precision switched the entry
 // points below to the mixed-precision solver (sm_cgbatchmp.cpp), which shares
@@ -36,57 +37,23 @@ using namespace sm;
 namespace sm_host {
 
 void batch_ws_free(BatchWs &w) {
-    for (double2 *&d : w.d) {
-        free_dev(d);
-        d = nullptr;
-    }
-    for (double2 *&a : w.a) {
-        free_dev(a);
-        a = nullptr;
-    }
-    free_dev(w.partials);
-    free_dev(w.sc);
-    if (w.h_sc) (void)hipHostFree(w.h_sc);
-    w.partials = nullptr;
-    w.sc = w.h_sc = nullptr;
+    w.bufs.release();
     w.K = 0;
     w.n = 0;
 }
 
-void cg_batch_free(sm_ctx *c) {
-    batch_ws_free(c->bt);
-    free_dev(c->bt_phi);
-    free_dev(c->bt_x);
-    free_dev(c->bt_src);
-    free_dev(c->bt_C);
-    c->bt_phi = c->bt_x = nullptr;
-    c->bt_src = nullptr;
-    c->bt_C = nullptr;
-    c->bt_pion_K = 0;
-}
-
 // Three d buffers, two Ad buffers (K x 16 n bytes each), partials and scalars.
-int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride, const char *who) {
+int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     batch_ws_free(w);
-    const size_t fb = sizeof(double2) * (size_t)n * (size_t)K;
-    const size_t pb = sizeof(double2) * (size_t)pstride * (size_t)K;
-    int rc = SM_OK;
-    for (double2 *&d : w.d)
-        if (rc == SM_OK) rc = alloc_dev((void **)&d, fb, who, "direction buffer");
-    for (double2 *&a : w.a)
-        if (rc == SM_OK) rc = alloc_dev((void **)&a, fb, who, "Ad buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, who, "partials");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sizeof(CGScalars) * (size_t)K, who, "scalars");
-    if (rc == SM_OK && hipHostMalloc((void **)&w.h_sc, sizeof(CGScalars) * (size_t)K) != hipSuccess) {
-        w.h_sc = nullptr;
-        (void)hipGetLastError();
-        rc = fail(SM_ERR_HIP, "%s: allocating %zu pinned bytes (scalars) failed", who, sizeof(CGScalars) * (size_t)K);
-    }
-    if (rc != SM_OK) {
-        batch_ws_free(w);
-        return rc;
-    }
+    const size_t fn = (size_t)n * (size_t)K, fb = sizeof(double2) * fn;
+    const size_t pn = (size_t)pstride * (size_t)K, pb = sizeof(double2) * pn;
+    BufGroup &b = w.bufs;
+    for (double2 *&d : w.d) TRY(b.add(&d, fn, BufKind::device, "direction buffer"));
+    for (double2 *&a : w.a) TRY(b.add(&a, fn, BufKind::device, "Ad buffer"));
+    TRY(b.add(&w.partials, pn, BufKind::device, "partials"));
+    TRY(b.add(&w.sc, (size_t)K, BufKind::device, "scalars"));
+    TRY(b.add(&w.h_sc, (size_t)K, BufKind::pinned, "pinned scalars"));
     // every buffer is read by halo lanes / rows before its first write: defined values
     for (double2 *d : w.d) HIP_TRY(hipMemsetAsync(d, 0, fb, c->stream));
     for (double2 *a : w.a) HIP_TRY(hipMemsetAsync(a, 0, fb, c->stream));
@@ -101,25 +68,19 @@ int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride, const cha
 static int batch_ready(sm_ctx *c, int K) {
     HIP_TRY(hipSetDevice(c->device));
     if (c->bt.K >= K) return SM_OK;
-    return batch_ws_alloc(c, c->bt, K, 2 * c->g.V, cg_batch_config(c->g, K, c->bt_tiles).pstride, kBatchWho);
+    return batch_ws_alloc(c, c->bt, K, 2 * c->g.V, cg_batch_config(c->g, K, c->bt_tiles).pstride);
 }
 
 // Device staging for the host-pointer entry and the correlator: phi and x, K columns.
 int batch_staging_ready(sm_ctx *c, int K) {
     if (c->bt_pion_K >= K) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_dev(c->bt_phi);
-    free_dev(c->bt_x);
-    c->bt_phi = c->bt_x = nullptr;
+    BufGroup &b = c->bt_stage_bufs;
+    b.release();
     c->bt_pion_K = 0;
-    const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
-    int rc = alloc_dev((void **)&c->bt_phi, fb, kBatchWho, "sources");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->bt_x, fb, kBatchWho, "solutions");
-    if (rc != SM_OK) {
-        free_dev(c->bt_phi);
-        c->bt_phi = nullptr;
-        return rc;
-    }
+    const size_t fn = 2 * (size_t)c->g.V * (size_t)K;
+    TRY(b.add(&c->bt_phi, fn, BufKind::device, "sources"));
+    TRY(b.add(&c->bt_x, fn, BufKind::device, "solutions"));
     c->bt_pion_K = K;
     return SM_OK;
 }
@@ -209,9 +170,10 @@ int sm_pion_correlator(sm_ctx *c, double m0, double tol, int max_iter, int nsrc,
     TRY(check_ready(c));
     HIP_TRY(hipSetDevice(c->device));
     if (!eo) TRY(batch_staging_ready(c, K));
-    if (!c->bt_src) TRY(alloc_dev((void **)&c->bt_src, sizeof(int) * kBatchMax, kBatchWho, "source coordinates"));
-    if (!c->bt_C) TRY(alloc_dev((void **)&c->bt_C, sizeof(double) * (kBatchMax / 2) * (size_t)c->g.Wt, kBatchWho,
-                                   "correlator"));
+    if (BufGroup &b = c->bt_corr_bufs; b.empty()) {
+        TRY(b.add(&c->bt_src, (size_t)kBatchMax, BufKind::device, "source coordinates"));
+        TRY(b.add(&c->bt_C, (kBatchMax / 2) * (size_t)c->g.Wt, BufKind::device, "correlator"));
+    }
     const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
     int *sx = c->bt_src, *st = c->bt_src + kBatchMax / 2;
     // pageable host memory: the copies have left the caller's arrays when they return

@@ -26,17 +26,6 @@ using namespace sm;
 
 namespace sm_host {
 
-void cg_batch_mixed_free(sm_ctx *c) {
-    CGBatchMixedWs &w = c->btmp;
-    for (void *p : {(void *)w.d[0], (void *)w.d[1], (void *)w.d[2], (void *)w.a[0], (void *)w.a[1], (void *)w.y,
-                    (void *)w.U, (void *)w.r, (void *)w.t, (void *)w.ax, (void *)w.partials, (void *)w.sc})
-        if (p) (void)hipFree(p);
-    if (w.h_sc) (void)hipHostFree(w.h_sc);
-    w = CGBatchMixedWs{};
-}
-
-constexpr const char *kWho = "mixed batched CG";  // the error prefix
-
 static size_t partials_per_column(const sm_ctx *c) {
     const BatchCfg cfg = cg_batch_config(c->g, 1, c->bt_tiles);  // P does not depend on K
     const size_t nbr = (size_t)batch_mp_blocks(c->g);
@@ -48,30 +37,21 @@ static int mixed_ready(sm_ctx *c, int K) {
     CGBatchMixedWs &w = c->btmp;
     if (w.K >= K) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    cg_batch_mixed_free(c);
-    const size_t n = 2 * (size_t)c->g.V, f32 = sizeof(float2) * n * (size_t)K, f64 = sizeof(double2) * n * (size_t)K;
-    const size_t pb = sizeof(double2) * partials_per_column(c) * (size_t)K, sb = sizeof(MPScalars) * (size_t)K;
-    int rc = SM_OK;
-    for (float2 *&d : w.d)
-        if (rc == SM_OK) rc = alloc_dev((void **)&d, f32, kWho, "direction buffer");
-    for (float2 *&a : w.a)
-        if (rc == SM_OK) rc = alloc_dev((void **)&a, f32, kWho, "Ad buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.y, f32, kWho, "correction");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.U, sizeof(float2) * n, kWho, "links");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.r, f64, kWho, "residual");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.t, f64, kWho, "D^dag x");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.ax, f64, kWho, "D D^dag x");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.partials, pb, kWho, "partials");
-    if (rc == SM_OK) rc = alloc_dev((void **)&w.sc, sb, kWho, "scalars");
-    if (rc == SM_OK && hipHostMalloc((void **)&w.h_sc, sb) != hipSuccess) {
-        w.h_sc = nullptr;
-        (void)hipGetLastError();
-        rc = fail(SM_ERR_HIP, "%s: allocating %zu pinned bytes (scalars) failed", kWho, sb);
-    }
-    if (rc != SM_OK) {
-        cg_batch_mixed_free(c);
-        return rc;
-    }
+    BufGroup &b = w.bufs;
+    b.release();
+    w.K = 0;
+    const size_t n = 2 * (size_t)c->g.V, nK = n * (size_t)K, f32 = sizeof(float2) * nK;
+    const size_t pn = partials_per_column(c) * (size_t)K, pb = sizeof(double2) * pn, sb = sizeof(MPScalars) * (size_t)K;
+    for (float2 *&d : w.d) TRY(b.add(&d, nK, BufKind::device, "direction buffer"));
+    for (float2 *&a : w.a) TRY(b.add(&a, nK, BufKind::device, "Ad buffer"));
+    TRY(b.add(&w.y, nK, BufKind::device, "correction"));
+    TRY(b.add(&w.U, n, BufKind::device, "links"));
+    TRY(b.add(&w.r, nK, BufKind::device, "residual"));
+    TRY(b.add(&w.t, nK, BufKind::device, "D^dag x"));
+    TRY(b.add(&w.ax, nK, BufKind::device, "D D^dag x"));
+    TRY(b.add(&w.partials, pn, BufKind::device, "partials"));
+    TRY(b.add(&w.sc, (size_t)K, BufKind::device, "scalars"));
+    TRY(b.add(&w.h_sc, (size_t)K, BufKind::pinned, "pinned scalars"));
     // the passes' halo lanes and rows read every buffer before its first write: defined values
     for (float2 *d : w.d) HIP_TRY(hipMemsetAsync(d, 0, f32, c->stream));
     for (float2 *a : w.a) HIP_TRY(hipMemsetAsync(a, 0, f32, c->stream));
@@ -133,8 +113,7 @@ struct BatchOps {
     void fold(ColMask m, ColMask discard) { launch_batch_mp_fold(c->stream, c->g, K, m, discard, x, w.y, w.d, w.sc); }
     // A e = r_b through the fp64 batched solver with K = 1 (its own x0 = r convention), x_b += e
     int finish(int b, double tol64, int iters, sm_cg_result *r64) {
-        if (c->bt.K < 1)
-            TRY(batch_ws_alloc(c, c->bt, 1, n, cg_batch_config(c->g, 1, c->bt_tiles).pstride, kBatchWho));
+        if (c->bt.K < 1) TRY(batch_ws_alloc(c, c->bt, 1, n, cg_batch_config(c->g, 1, c->bt_tiles).pstride));
         double2 *e = w.t + b * n;
         TRY(cg_batch_solve(c, c->bt, 1, w.r + b * n, e, links, tol64, iters, r64));
         launch_mp_add(c->stream, n, x + b * n, e);

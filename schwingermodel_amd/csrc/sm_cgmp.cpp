@@ -21,26 +21,18 @@ using namespace sm;
 
 namespace sm_host {
 
-void mixed_free(sm_ctx *c, MixedWs &w) {
-    for (float2 *p : {w.d[0], w.d[1], w.d[2], w.a[0], w.a[1], w.U[0], w.U[1], w.y}) stream_free(c, p);
-    for (void *p : {(void *)w.w, (void *)w.fb, (void *)w.partials, (void *)w.sc})
-        if (p) (void)hipFree(p);
-    if (w.h_sc) (void)hipHostFree(w.h_sc);
-    w = MixedWs{};
-}
-
 // The fp32 buffers, at the first mixed solve (placed like the fp64 pass's
 // streamed buffers); the fp32 links again after every change of U.
 static int mixed_ready(sm_ctx *c) {
     MixedWs &w = c->mp;
-    const size_t fb = sizeof(float2) * 2 * (size_t)c->g.V;
-    if (!w.sc) {
-        for (float2 *&d : w.d) HIP_TRY(stream_malloc(c, (void **)&d, fb));
-        HIP_TRY(stream_malloc(c, (void **)&w.y, fb));
-        HIP_TRY(stream_malloc(c, (void **)&w.U[0], fb));
-        HIP_TRY(hipMalloc(&w.partials, sizeof(double2) * 2 * (size_t)kMaxPartials));
-        HIP_TRY(hipHostMalloc(&w.h_sc, sizeof(MPScalars)));
-        HIP_TRY(hipMalloc(&w.sc, sizeof(MPScalars)));
+    const size_t n = 2 * (size_t)c->g.V;
+    if (BufGroup &b = w.bufs; b.empty()) {
+        for (float2 *&d : w.d) TRY(b.add(&d, n, BufKind::streamed, "direction buffer"));
+        TRY(b.add(&w.y, n, BufKind::streamed, "correction"));
+        TRY(b.add(&w.U[0], n, BufKind::streamed, "links"));
+        TRY(b.add(&w.partials, 2 * (size_t)kMaxPartials, BufKind::device, "partials"));
+        TRY(b.add(&w.h_sc, 1, BufKind::pinned, "pinned scalars"));
+        TRY(b.add(&w.sc, 1, BufKind::device, "scalars"));
         HIP_TRY(hipMemsetAsync(w.sc, 0, sizeof(MPScalars), c->stream));
         launch_mp_zero(c->stream, 2 * c->g.V, w.y);
         w.U_valid = false;

@@ -342,7 +342,7 @@ static int peer_sums_setup(sm_ctx *c, const std::function<int(char *, size_t)> &
     std::vector<char> hh(hb * P, 0);
     if (hipExtMallocWithFlags((void **)&c->peer_region, kPeerHdrBytes, hipDeviceMallocUncached) != hipSuccess ||
         hipMemset(c->peer_region, 0, kPeerHdrBytes) != hipSuccess ||
-        (!c->peer_view_dev && hipMalloc(&c->peer_view_dev, sizeof(PeerView)) != hipSuccess) ||
+        (!c->peer_view_dev && buf_raw_alloc(c, BufKind::device, (void **)&c->peer_view_dev, sizeof(PeerView))) ||
         hipIpcGetMemHandle(reinterpret_cast<hipIpcMemHandle_t *>(hh.data() + hb * me), c->peer_region) != hipSuccess)
         ok = 0;
     (void)hipGetLastError();
@@ -394,7 +394,7 @@ static int peer_sums_setup(sm_ctx *c, const std::function<int(char *, size_t)> &
             (void)hipIpcCloseMemHandle(p);
             p = nullptr;
         }
-    if (c->peer_region) (void)hipFree(c->peer_region);
+    buf_raw_free(c, BufKind::device, c->peer_region);
     c->peer_region = nullptr;
     (void)hipGetLastError();
     return rc;
@@ -406,11 +406,9 @@ int rccl_peer_sums_setup(sm_ctx *c) {
     const int P = c->loop ? 1 : c->nshard, me = c->loop ? 0 : c->shard;
     char *dh = nullptr;  // the handles on the device for the all-gather
     int *flag = nullptr;
-    HIP_TRY(hipMalloc(&dh, sizeof(hipIpcMemHandle_t) * P));
-    if (hipMalloc(&flag, sizeof(int)) != hipSuccess) {
-        (void)hipFree(dh);
-        return fail(SM_ERR_HIP, "peer sums: allocation failed");
-    }
+    BufGroup bufs("peer sums");  // freed on return
+    TRY(bufs.add(&dh, sizeof(hipIpcMemHandle_t) * P, BufKind::device, "handles"));
+    TRY(bufs.add(&flag, 1, BufKind::device, "flag"));
     auto gather = [&](char *bytes, size_t nb) -> int {  // in place, over the communicator
         HIP_TRY(hipMemcpy(dh, bytes, nb * P, hipMemcpyHostToDevice));
         NCCL_TRY(ncclAllGather(dh + nb * me, dh, nb, ncclUint8, c->comm, c->stream));
@@ -425,10 +423,7 @@ int rccl_peer_sums_setup(sm_ctx *c) {
         HIP_TRY(hipStreamSynchronize(c->stream));
         return SM_OK;
     };
-    const int rc = peer_sums_setup(c, gather, agree);
-    (void)hipFree(dh);
-    (void)hipFree(flag);
-    return rc;
+    return peer_sums_setup(c, gather, agree);
 }
 
 // The same for a host-staged context (test option hosted_psums=1): the RCCL

@@ -12,10 +12,13 @@
 #include <cstdio>
 #include <vector>
 
+#include "sm_buf.h"
 #include "sm_internal.h"
 #include "sm_peer.h"
 
 namespace sm_host {  // fail, TRY: sm_cg_host.h (through sm_internal.h)
+
+constexpr const char *kBatchWho = "batched CG", *kEoBatchWho = "batched even-odd CG";  // their error prefixes
 
 #define HIP_TRY(expr)                                                                   \
     do {                                                                                \
@@ -44,8 +47,11 @@ enum { F_IN, F_OUT, F_TMP, F_X, F_R, F_D, F_D2, F_T, F_AD, F_PHI, F_L, F_RR, F_A
 // Workspace of an fp64 batched CG solve of up to K columns of n complex, the
 // full-lattice solver's (sm_cgbatch.cpp, n = 2V) or the even-odd one's
 // (sm_eobatch.cpp, n = V): the context owns one of each for sm_cg_batch and
-// sm_eo_cg_batch, a replica ensemble (sm_ens.cpp) its own.
+// sm_eo_cg_batch, a replica ensemble (sm_ens.cpp) its own. bufs owns every
+// pointer (batch_ws_alloc); who: the solver's error prefix.
 struct BatchWs {
+    explicit BatchWs(const char *who) : bufs(who) {}
+    sm_host::BufGroup bufs;
     int K = 0;                      // columns it holds
     long n = 0;                     // complex per column
     double2 *d[3] = {};             // d_i in d[i mod 3], K x n complex each
@@ -57,8 +63,11 @@ struct BatchWs {
 // State of a mixed-precision solver (sm_cgmp.cpp on the full lattice,
 // sm_eomp.cpp on one parity): its own directions, y, links, partials and
 // scalars, from the first mixed solve on; nothing shared with the fp64 paths.
-// n = the solver's vector length in complex entries (2V / V).
+// n = the solver's vector length in complex entries (2V / V). bufs owns every
+// pointer but fb, which is fin's: a failed fallback request leaves the rest.
 struct MixedWs {
+    MixedWs(const char *who, sm_ctx *c) : bufs(who, c), fin(who) {}
+    sm_host::BufGroup bufs, fin;
     float2 *d[3] = {};              // the three direction buffers, n float2 each
     float2 *a[2] = {};              // even-odd: Ad_j by pass parity
     float2 *y = nullptr;            // the fp32 correction to x
@@ -74,8 +83,10 @@ struct MixedWs {
 // State of the mixed-precision batched solver (sm_cgbatchmp.cpp) for K columns:
 // its own fp32 directions, Ad, y and links, the fp64 work of the true residual,
 // partials and scalars; nothing shared with the fp64 batch but the K = 1
-// workspace of the rare fp64 finish (sm_ctx::bt, whatever it holds).
+// workspace of the rare fp64 finish (sm_ctx::bt, whatever it holds). bufs owns
+// every pointer.
 struct CGBatchMixedWs {
+    sm_host::BufGroup bufs{"mixed batched CG"};
     int K = 0;                      // columns it holds
     float2 *d[3] = {};              // the direction ring, K x 2V float2 each
     float2 *a[2] = {};              // Ad by pass parity
@@ -86,6 +97,11 @@ struct CGBatchMixedWs {
     sm::MPScalars *sc = nullptr, *h_sc = nullptr;  // K each: device, pinned host mirror
 };
 
+// Every buffer allocated after creation belongs to a BufGroup (sm_buf.h) next to
+// its pointers: one group per capacity, built whole or not at all, tested with
+// empty() and freed by its destructor at sm_destroy's `delete`, after the
+// streams were synchronised. The creation-time buffers (U, fields[], faces,
+// scalars, pinned mirrors, Uang, the peer region) are sm_destroy's own.
 struct sm_ctx {
     int device = 0;
     int nshard = 1, shard = 0;
@@ -136,6 +152,7 @@ struct sm_ctx {
     double place_us[16] = {};       // the initial set, then one per buffer searched (up to 3 sweeps of 4)
     double *Uang = nullptr;         // 2V link codes (plane mu0 then mu1)
     double *Uang_face = nullptr;    // t-shards: codes of the 4-deep ghost links (16 Nx)
+    sm_host::BufGroup uang_face_bufs{"link codes"};
     hipStream_t own_stream = nullptr, stream = nullptr;
     hipStream_t comm_stream = nullptr;  // halo exchange overlapped with interior compute (hosted: == stream)
     bool own_comm_stream = false;       // comm_stream created by (and destroyed with) this context
@@ -213,11 +230,13 @@ struct sm_ctx {
     double2 *U_alt = nullptr;       // 2V: the other gauge buffer (leapfrog copy / kept conf)
     double *Pmd = nullptr;          // 2V: momenta
     double *Fmd = nullptr;          // 2V: MD force
+    sm_host::BufGroup md_bufs{"molecular dynamics"};
     // even-odd action (sm_eo.cpp; allocated on first use)
     double2 *eo = nullptr;          // checkerboard work vectors, V complex each
     double2 *Ucb = nullptr;         // gauge field in checkerboard layout (even, odd)
     double2 *eo_faces = nullptr;    // t-sharded: checkerboard face slots (sm_eo.cpp)
     double2 *eo_faces4 = nullptr;   // t-sharded: 4-deep checkerboard face slots of the one-pass eo CG
+    sm_host::BufGroup eo_bufs{"even-odd action"};
     int eo_fused = 1;               // Dhat as one fused marching pass (0: two hop launches)
     int eo_cg_td = 1;               // even-odd CG: the one-pass two-direction kernel (sm_eotd.hip, one shard;
                                     // 0.54 vs 0.94 ms per iteration at 4096^2 for the six launches)
@@ -238,19 +257,19 @@ struct sm_ctx {
     int cg_precision = 0;
     double mp_delta = 0.1;          // update when the iterated |r| < mp_delta * its maximum (test option mp_delta_pct)
     int mp_force_fallback = 0;      // test option: take the fp64 finish after the first update
-    MixedWs mp;                     // info: the last sm_cg_dev
+    MixedWs mp{"mixed-precision CG", this};  // info: the last sm_cg_dev
     // mixed-precision even-odd CG (sm_eomp.cpp; one shard): every even-odd
     // solve runs fp32 inner iterations (sm_eosp.hip) with fp64 reliable updates
     // when eo_cg_precision == 1. Independent of cg_precision; shares only the
     // test options mp_delta / mp_force_fallback. Neither eo / sc / partials /
     // tick nor the mp state above is touched by the fp32 side.
     int eo_cg_precision = 0;
-    MixedWs eomp;                   // info: the last even-odd solve
+    MixedWs eomp{"mixed-precision even-odd CG", this};  // info: the last even-odd solve
     // batched multi-source CG (sm_cgbatch.cpp; one shard): its own directions,
     // Ad buffers, scalars and partials for bt.K columns, from the first batched
     // solve on and regrown for a larger K. Reads c->U at every call; keeps
     // nothing that depends on the gauge field.
-    BatchWs bt;                     // the solver's workspace
+    BatchWs bt{sm_host::kBatchWho};  // the solver's workspace
     int bt_tiles = 0;               // test option batch_tiles=N: tiles per launch aimed at (0: kBatchTargetTiles)
     // sm_cg_batch(_dev) and the correlator's solve run fp32 inner iterations with
     // fp64 reliable updates when bt_precision == 1 (sm_cgbatchmp.cpp). Independent
@@ -262,20 +281,24 @@ struct sm_ctx {
     // pion correlator: sources / solutions (bt_pion_K columns), source coordinates, C
     int bt_pion_K = 0;
     double2 *bt_phi = nullptr, *bt_x = nullptr;
+    sm_host::BufGroup bt_stage_bufs{sm_host::kBatchWho};  // bt_phi, bt_x
     int *bt_src = nullptr;          // 2 x kBatchMax / 2 ints
     double *bt_C = nullptr;         // kBatchMax / 2 x Wt
+    sm_host::BufGroup bt_corr_bufs{sm_host::kBatchWho};   // bt_src, bt_C
 
     // batched even-odd CG (sm_eobatch.cpp; one shard, fp64): its own workspace
     // for eob.K columns, the checkerboard copy of U it makes at every call, the
     // columns' even parts (eob_K columns) and the host-pointer entry's
     // full-layout staging (eob_fK columns), all from the first call on. Shares
     // nothing with eo / Ucb, the mixed solvers, bt or the stepwise solver.
-    BatchWs eob;
+    BatchWs eob{sm_host::kEoBatchWho};
     int eob_tiles = 0;              // test option eo_batch_tiles=N: tiles per launch aimed at (0: kEoBatchTargetTiles)
     double2 *eob_U = nullptr;       // even links, then odd links: 2V complex
     int eob_K = 0, eob_fK = 0;
     double2 *eob_phi = nullptr, *eob_x = nullptr;    // eob_K x V complex
     double2 *eob_fphi = nullptr, *eob_fx = nullptr;  // eob_fK x 2V complex
+    sm_host::BufGroup eob_U_bufs{sm_host::kEoBatchWho}, eob_half_bufs{sm_host::kEoBatchWho},  // eob_U; eob_phi, eob_x
+        eob_full_bufs{sm_host::kEoBatchWho};                                                   // eob_fphi, eob_fx
 
     // sm_pion_correlator through the even-odd system (sm_pion_solver = 1; sm_pion.cpp):
     // five half-lattice fields and the full-layout propagators for pn_K columns, from
@@ -283,6 +306,7 @@ struct sm_ctx {
     int pion_solver = 0;
     int pn_K = 0;
     double2 *pn_buf = nullptr;      // pn_K x 7V complex
+    sm_host::BufGroup pn_bufs{sm_host::kEoBatchWho};
 
     // topological charge and Wilson flow (sm_flow.cpp). sm_topology works in
     // partials / sums; a flow (one shard) in two field buffers and one
@@ -291,12 +315,14 @@ struct sm_ctx {
     double *fl_A = nullptr;         // 2V doubles
     double *fl_series = nullptr;    // 3 doubles per measured point, regrown for a longer series
     long fl_points = 0;
+    sm_host::BufGroup fl_bufs{"Wilson flow"}, fl_series_bufs{"Wilson flow"};  // fl_W, fl_A; fl_series
 
     // stochastic quark loops (sm_loops.cpp), from the first call on: the columns' (seed, k) and the
     // loops of lp_cols columns on the device. Solves and fields are the batched CG's / the pion's above.
     uint64_t *lp_sk = nullptr;      // 2 x kBatchMax: seeds, then vector numbers
     double *lp_out = nullptr;       // lp_cols x Wt x 4
     size_t lp_cols = 0;
+    sm_host::BufGroup lp_sk_bufs{"quark loops"}, lp_out_bufs{"quark loops"};
 
     double2 *field(int i) { return fields[i]; }
 };
@@ -376,7 +402,6 @@ int placement_probe_default();            // candidates per buffer for new conte
 // to when the context's cg_precision is 1 (sm_cgmp.cpp)
 int cg_dev_fp64(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
 int cg_dev_mixed(sm_ctx *c, const double *phi, double *x, double m0, double tol, int max_iter, sm_cg_result *res);
-void mixed_free(sm_ctx *c, MixedWs &w);  // either mixed solver's state
 // The device calls of a one-column mixed solve (sm_cg_host.h MixedColumn) that
 // do not depend on the operator. A solver adds true_residual, pass, fold and
 // solve64 on its own.
@@ -413,23 +438,17 @@ struct MixedDev {
         return read();
     }
     int finish_vectors(double2 **rhs, double2 **e) {
-        if (!w.fb) HIP_TRY(hipMalloc(&w.fb, sizeof(double2) * 2 * (size_t)n));
+        if (w.fin.empty()) TRY(w.fin.add(&w.fb, 2 * (size_t)n, BufKind::device, "finish vectors"));
         *rhs = w.fb;
         *e = w.fb + n;
         return SM_OK;
     }
 };
-// hipFree of a pointer that may be null; hipMalloc that reports the request as
-// "<who>: allocating ... (<what>) failed" and leaves no sticky error (sm_capi.cpp)
-void free_dev(void *p);
-int alloc_dev(void **p, size_t bytes, const char *who, const char *what);
-
 // ---- the fp64 batched CG hosts (sm_cgbatch.cpp, sm_eobatch.cpp) ----
-constexpr const char *kBatchWho = "batched CG", *kEoBatchWho = "batched even-odd CG";  // their error prefixes
 // A workspace for K columns of n complex with pstride complex of partials per
 // column (the solver's BatchCfg::pstride, which does not depend on K), zeroed;
-// SM_ERR_HIP names the bytes under `who` on failure and leaves w empty.
-int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride, const char *who);
+// SM_ERR_HIP names the bytes under w's `who` on failure and leaves w empty.
+int batch_ws_alloc(sm_ctx *c, BatchWs &w, int K, long n, long pstride);
 void batch_ws_free(BatchWs &w);
 // The host of both solvers, the only copy: init(dbuf) starts the columns (x =
 // phi, d_0 where pass 0 expects d_{-1}, the scalars), then up to max_iter + 1
@@ -475,19 +494,17 @@ int batch_cg_solve(sm_ctx *c, const BatchWs &w, const BatchCfg &cfg, int K, doub
 }
 // The two entry points on any such workspace: K columns of phi -> x, column b
 // on l's links and mass (even-odd: even vectors, V complex apart, on l's
-// checkerboard links); and what frees the context's workspaces and staging.
+// checkerboard links).
 int cg_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const BatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res);
 int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res);
-void cg_batch_free(sm_ctx *c);  // the batched CG's and the pion correlator's (sm_cgbatch.cpp)
 // (sm_cgbatch.cpp) the context's device staging bt_phi / bt_x for K columns; and every batched solve
 // of its entry points: K columns of phi -> x on the context's field with m0, fp64 on c->bt or the
 // mixed solver (sm_cg_batch_precision), c->bt_info = the columns' reports
 int batch_staging_ready(sm_ctx *c, int K);
 int batch_solve(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
                 sm_cg_result *res);
-void eo_batch_free(sm_ctx *c);
 // The context's even-odd batch workspace for K columns and its checkerboard link buffer (sm_eobatch.cpp)
 int eob_ready(sm_ctx *c, int K);
 // ---- the pion correlator's even-odd path (sm_pion.cpp) ----
@@ -508,14 +525,10 @@ int pion_eo_ready(sm_ctx *c, int K);
 // sm_pion_correlator's body in mode 1 (arguments checked by the caller; sx / st: device)
 int pion_correlator_eo(sm_ctx *c, double m0, double tol, int max_iter, int nsrc, const int *sx, const int *st,
                        double *C, sm_cg_result *res);
-void pion_free(sm_ctx *c);
-void flow_free(sm_ctx *c);  // the Wilson flow's buffers (sm_flow.cpp)
-void loops_free(sm_ctx *c); // the quark loops' buffers (sm_loops.cpp)
 // The mixed-precision batched solve on the context's gauge field (sm_cgbatchmp.cpp):
 // K columns of phi -> x on the device, c->bt_info[b] = column b's report.
 int cg_batch_mixed(sm_ctx *c, int K, const double2 *phi, double2 *x, double m0, double tol, int max_iter,
                    sm_cg_result *res);
-void cg_batch_mixed_free(sm_ctx *c);
 
 // even-odd preconditioned pseudofermion action (sm_eo.cpp); phi / chi in the
 // full layout, only their even sites used

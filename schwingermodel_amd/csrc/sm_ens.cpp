@@ -47,14 +47,6 @@ using namespace sm_host;
 
 namespace sm_host {
 
-int ens_alloc(void **p, size_t bytes, const char *what, bool pinned) {
-    const hipError_t err = pinned ? hipHostMalloc(p, bytes) : hipMalloc(p, bytes);
-    if (err == hipSuccess) return SM_OK;
-    *p = nullptr;
-    (void)hipGetLastError();
-    return fail(SM_ERR_HIP, "ensemble: allocating %zu bytes (%s) failed: %s", bytes, what, hipGetErrorString(err));
-}
-
 int all_have(const sm_ens *e) {
     for (int r = 0; r < e->R; ++r)
         if (!e->have[(size_t)r])
@@ -66,20 +58,18 @@ int all_have(const sm_ens *e) {
 // The even-odd action's fields: 32 B per site and replica of checkerboard
 // links, 96 of half-lattice fields and 80 of the batched solver's workspace.
 int eo_fields_ready(sm_ens *e) {
-    if (e->eh) return SM_OK;
+    BufGroup &b = e->eo_bufs;
+    if (!b.empty()) return SM_OK;
     sm_ctx *c = e->c;
-    const size_t hb = sizeof(double2) * (size_t)c->g.V * (size_t)e->R;
-    int rc = ens_alloc((void **)&e->Ucb, 2 * hb, "checkerboard links");
-    if (rc == SM_OK)
-        rc = batch_ws_alloc(c, e->eows, e->R, c->g.V, eo_batch_config(c->g, e->R, c->eob_tiles).pstride, kEoBatchWho);
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->eh, EH_N * hb, "even-odd fields");
-    if (rc != SM_OK) {
-        if (e->Ucb) (void)hipFree(e->Ucb);
-        e->Ucb = nullptr;
+    const size_t hn = (size_t)c->g.V * (size_t)e->R;
+    int rc = b.add(&e->Ucb, 2 * hn, BufKind::device, "checkerboard links");
+    if (rc == SM_OK) rc = batch_ws_alloc(c, e->eows, e->R, c->g.V, eo_batch_config(c->g, e->R, c->eob_tiles).pstride);
+    if (rc == SM_OK) rc = b.add(&e->eh, EH_N * hn, BufKind::device, "even-odd fields");
+    if (rc != SM_OK) {  // each owner emptied itself; here the other one
+        b.release();
         batch_ws_free(e->eows);
-        return rc;
     }
-    return SM_OK;
+    return rc;
 }
 
 }  // namespace sm_host
@@ -90,19 +80,6 @@ struct HTerms {
     double H, sp, action;
     int iterations, converged;
 };
-
-void ens_free(sm_ens *e) {
-    void *dev[] = {e->U, e->Ubak, e->chi, e->phi, e->x,   e->P,  e->F,
-                   e->par, e->massv, e->part, e->sums, e->Ucb, e->eh, e->pn_src, e->pn_C, e->fl_series, e->lp_sk, e->lp_out};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *host[] = {e->h_par, e->h_mass, e->h_sums};
-    for (void *p : host)
-        if (p) (void)hipHostFree(p);
-    batch_ws_free(e->ws);
-    batch_ws_free(e->eows);
-    delete e;
-}
 
 int ens_check(const sm_ens *e, int r) {
     if (!e) return fail(SM_ERR_ARG, "null ensemble");
@@ -184,26 +161,28 @@ int sm_ens_create(sm_ctx *c, int R, sm_ens **out) {
     e->c = c;
     e->R = R;
     e->have.assign((size_t)R, 0);
-    const size_t fb = sizeof(double2) * slab_complex(e) * (size_t)R, rb = fb / 2;
+    const size_t fn = slab_complex(e) * (size_t)R;  // complex of R fields = doubles of R momenta
     const size_t nsum = 3 * (size_t)R, np = nsum * (size_t)gauge_reduce_blocks(c->g);
-    int rc = ens_alloc((void **)&e->U, fb, "gauge fields");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->Ubak, fb, "kept gauge fields");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->chi, fb, "chi");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->phi, fb, "phi");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->x, fb, "solutions");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->P, rb, "momenta");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->F, rb, "forces");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->par, sizeof(EnsPar) * (size_t)R, "parameters");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->massv, sizeof(double) * (size_t)R, "masses");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->part, sizeof(double2) * np, "partials");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->sums, sizeof(double2) * nsum, "sums");
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->h_par, sizeof(EnsPar) * (size_t)R, "pinned parameters", true);
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->h_mass, sizeof(double) * (size_t)R, "pinned masses", true);
-    if (rc == SM_OK) rc = ens_alloc((void **)&e->h_sums, sizeof(double2) * nsum, "pinned sums", true);
-    if (rc == SM_OK)
-        rc = batch_ws_alloc(c, e->ws, R, 2 * c->g.V, cg_batch_config(c->g, R, c->bt_tiles).pstride, kBatchWho);
+    const int rc = [&] {
+        BufGroup &b = e->bufs;
+        TRY(b.add(&e->U, fn, BufKind::device, "gauge fields"));
+        TRY(b.add(&e->Ubak, fn, BufKind::device, "kept gauge fields"));
+        TRY(b.add(&e->chi, fn, BufKind::device, "chi"));
+        TRY(b.add(&e->phi, fn, BufKind::device, "phi"));
+        TRY(b.add(&e->x, fn, BufKind::device, "solutions"));
+        TRY(b.add(&e->P, fn, BufKind::device, "momenta"));
+        TRY(b.add(&e->F, fn, BufKind::device, "forces"));
+        TRY(b.add(&e->par, (size_t)R, BufKind::device, "parameters"));
+        TRY(b.add(&e->massv, (size_t)R, BufKind::device, "masses"));
+        TRY(b.add(&e->part, np, BufKind::device, "partials"));
+        TRY(b.add(&e->sums, nsum, BufKind::device, "sums"));
+        TRY(b.add(&e->h_par, (size_t)R, BufKind::pinned, "pinned parameters"));
+        TRY(b.add(&e->h_mass, (size_t)R, BufKind::pinned, "pinned masses"));
+        TRY(b.add(&e->h_sums, nsum, BufKind::pinned, "pinned sums"));
+        return batch_ws_alloc(c, e->ws, R, 2 * c->g.V, cg_batch_config(c->g, R, c->bt_tiles).pstride);
+    }();
     if (rc != SM_OK) {
-        ens_free(e);
+        delete e;
         return rc;
     }
     *out = e;
@@ -214,7 +193,7 @@ int sm_ens_destroy(sm_ens *e) {
     if (!e) return fail(SM_ERR_ARG, "null ensemble");
     (void)hipSetDevice(e->c->device);
     (void)hipStreamSynchronize(e->c->stream);
-    ens_free(e);
+    delete e;  // the BufGroups free here
     return SM_OK;
 }
 

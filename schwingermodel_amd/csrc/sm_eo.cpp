@@ -101,12 +101,11 @@ int eo_ready(sm_ctx *c) {
                     c->g.Wt);
     if (c->sharded() && c->g.Wt < 4)
         return fail(SM_ERR_ARG, "even-odd preconditioning needs t-shards at least 4 wide (Wt = %d)", c->g.Wt);
-    if (!c->eo) {
-        HIP_TRY(hipMalloc(&c->eo, sizeof(double2) * (size_t)EO_N * c->g.V));
-        HIP_TRY(hipMalloc(&c->Ucb, sizeof(double2) * 2 * (size_t)c->g.V));
-        if (c->sharded()) HIP_TRY(hipMalloc(&c->eo_faces, sizeof(double2) * (size_t)EOF_N * 8 * c->g.Nx));
-        if (eo_td_sharded_ok(c))
-            HIP_TRY(hipMalloc(&c->eo_faces4, sizeof(double2) * (size_t)EOF4_N * 16 * c->g.Nx));
+    if (BufGroup &b = c->eo_bufs; b.empty()) {
+        TRY(b.add(&c->eo, (size_t)EO_N * c->g.V, BufKind::device, "work vectors"));
+        TRY(b.add(&c->Ucb, 2 * (size_t)c->g.V, BufKind::device, "checkerboard links"));
+        if (c->sharded()) TRY(b.add(&c->eo_faces, (size_t)EOF_N * 8 * c->g.Nx, BufKind::device, "faces"));
+        if (eo_td_sharded_ok(c)) TRY(b.add(&c->eo_faces4, (size_t)EOF4_N * 16 * c->g.Nx, BufKind::device, "4-deep faces"));
     }
     // checkerboard copy of the current gauge field (U changes between calls)
     launch_to_cb(c->stream, c->g, c->U, ucb(c, 0), ucb(c, 1));

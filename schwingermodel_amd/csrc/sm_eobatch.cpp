@@ -29,17 +29,6 @@ using namespace sm;
 
 namespace sm_host {
 
-void eo_batch_free(sm_ctx *c) {
-    batch_ws_free(c->eob);
-    free_dev(c->eob_U);
-    free_dev(c->eob_phi);
-    free_dev(c->eob_x);
-    free_dev(c->eob_fphi);
-    free_dev(c->eob_fx);
-    c->eob_U = c->eob_phi = c->eob_x = c->eob_fphi = c->eob_fx = nullptr;
-    c->eob_K = c->eob_fK = 0;
-}
-
 int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, double2 *x, const EoBatchLinks &l,
                    double tol, int max_iter, sm_cg_result *res) {
     const BatchCfg cfg = eo_batch_config(c->g, K, c->eob_tiles);
@@ -58,22 +47,17 @@ int eo_batch_solve(sm_ctx *c, const BatchWs &w, int K, const double2 *phi, doubl
 int eob_ready(sm_ctx *c, int K) {
     HIP_TRY(hipSetDevice(c->device));
     if (c->eob.K < K)
-        TRY(batch_ws_alloc(c, c->eob, K, c->g.V, eo_batch_config(c->g, K, c->eob_tiles).pstride, kEoBatchWho));
-    if (!c->eob_U) TRY(alloc_dev((void **)&c->eob_U, sizeof(double2) * 2 * (size_t)c->g.V, kEoBatchWho, "checkerboard links"));
+        TRY(batch_ws_alloc(c, c->eob, K, c->g.V, eo_batch_config(c->g, K, c->eob_tiles).pstride));
+    if (c->eob_U_bufs.empty())
+        TRY(c->eob_U_bufs.add(&c->eob_U, 2 * (size_t)c->g.V, BufKind::device, "checkerboard links"));
     if (c->eob_K >= K) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_dev(c->eob_phi);
-    free_dev(c->eob_x);
-    c->eob_phi = c->eob_x = nullptr;
+    BufGroup &b = c->eob_half_bufs;
+    b.release();
     c->eob_K = 0;
-    const size_t hb = sizeof(double2) * (size_t)c->g.V * (size_t)K;
-    int rc = alloc_dev((void **)&c->eob_phi, hb, kEoBatchWho, "even sources");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->eob_x, hb, kEoBatchWho, "even solutions");
-    if (rc != SM_OK) {
-        free_dev(c->eob_phi);
-        c->eob_phi = nullptr;
-        return rc;
-    }
+    const size_t hn = (size_t)c->g.V * (size_t)K;
+    TRY(b.add(&c->eob_phi, hn, BufKind::device, "even sources"));
+    TRY(b.add(&c->eob_x, hn, BufKind::device, "even solutions"));
     c->eob_K = K;
     return SM_OK;
 }
@@ -82,18 +66,12 @@ int eob_ready(sm_ctx *c, int K) {
 static int eob_staging_ready(sm_ctx *c, int K) {
     if (c->eob_fK >= K) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_dev(c->eob_fphi);
-    free_dev(c->eob_fx);
-    c->eob_fphi = c->eob_fx = nullptr;
+    BufGroup &b = c->eob_full_bufs;
+    b.release();
     c->eob_fK = 0;
-    const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V * (size_t)K;
-    int rc = alloc_dev((void **)&c->eob_fphi, fb, kEoBatchWho, "sources");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->eob_fx, fb, kEoBatchWho, "solutions");
-    if (rc != SM_OK) {
-        free_dev(c->eob_fphi);
-        c->eob_fphi = nullptr;
-        return rc;
-    }
+    const size_t fn = 2 * (size_t)c->g.V * (size_t)K;
+    TRY(b.add(&c->eob_fphi, fn, BufKind::device, "sources"));
+    TRY(b.add(&c->eob_fx, fn, BufKind::device, "solutions"));
     c->eob_fK = K;
     return SM_OK;
 }

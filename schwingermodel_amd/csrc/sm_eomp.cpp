@@ -30,16 +30,15 @@ namespace sm_host {
 static int eo_mixed_ready(sm_ctx *c) {
     MixedWs &w = c->eomp;
     const size_t n = (size_t)c->g.V;  // complex entries of a one-parity field
-    const size_t fb = sizeof(float2) * n;
-    if (!w.sc) {
-        for (float2 *&d : w.d) HIP_TRY(stream_malloc(c, (void **)&d, fb));
-        for (float2 *&a : w.a) HIP_TRY(stream_malloc(c, (void **)&a, fb));
-        for (float2 *&u : w.U) HIP_TRY(stream_malloc(c, (void **)&u, fb));
-        HIP_TRY(stream_malloc(c, (void **)&w.y, fb));
-        HIP_TRY(hipMalloc(&w.w, sizeof(double2) * 3 * n));
-        HIP_TRY(hipMalloc(&w.partials, sizeof(double2) * 2 * (size_t)kMaxPartials));
-        HIP_TRY(hipHostMalloc(&w.h_sc, sizeof(MPScalars)));
-        HIP_TRY(hipMalloc(&w.sc, sizeof(MPScalars)));
+    if (BufGroup &b = w.bufs; b.empty()) {
+        for (float2 *&d : w.d) TRY(b.add(&d, n, BufKind::streamed, "direction buffer"));
+        for (float2 *&a : w.a) TRY(b.add(&a, n, BufKind::streamed, "Ad buffer"));
+        for (float2 *&u : w.U) TRY(b.add(&u, n, BufKind::streamed, "links"));
+        TRY(b.add(&w.y, n, BufKind::streamed, "correction"));
+        TRY(b.add(&w.w, 3 * n, BufKind::device, "fp64 work vectors"));
+        TRY(b.add(&w.partials, 2 * (size_t)kMaxPartials, BufKind::device, "partials"));
+        TRY(b.add(&w.h_sc, 1, BufKind::pinned, "pinned scalars"));
+        TRY(b.add(&w.sc, 1, BufKind::device, "scalars"));
         HIP_TRY(hipMemsetAsync(w.sc, 0, sizeof(MPScalars), c->stream));
         launch_mp_zero(c->stream, (long)n, w.y);
         w.U_valid = false;

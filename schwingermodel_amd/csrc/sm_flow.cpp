@@ -33,7 +33,6 @@ using namespace sm_host;
 
 namespace {
 
-constexpr const char *kWho = "Wilson flow";
 constexpr double kTwoPi = 6.283185307179586476925286766559;
 
 // measured points of a flow, or -1 for parameters no flow runs with
@@ -61,13 +60,12 @@ void to_topo(sm_topo *t, long n) {
 }
 
 // a device series of R x points x 3 doubles, kept and regrown for a longer one
-int series_ready(sm_ctx *c, double **buf, long *have, int R, long points) {
-    if (*buf && *have >= points) return SM_OK;
+int series_ready(sm_ctx *c, BufGroup &b, double **buf, long *have, int R, long points) {
+    if (!b.empty() && *have >= points) return SM_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));
-    free_dev(*buf);
-    *buf = nullptr;
+    b.release();
     *have = 0;
-    TRY(alloc_dev((void **)buf, sizeof(double) * 3 * (size_t)R * (size_t)points, kWho, "series"));
+    TRY(b.add(buf, 3 * (size_t)R * (size_t)points, BufKind::device, "series"));
     *have = points;
     return SM_OK;
 }
@@ -116,35 +114,14 @@ int one_shard(const sm_ctx *c) {
 }
 
 int flow_buffers_ready(sm_ctx *c) {
-    if (c->fl_A) return SM_OK;
-    const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V;
-    int rc = alloc_dev((void **)&c->fl_W[0], fb, kWho, "field buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->fl_W[1], fb, kWho, "field buffer");
-    if (rc == SM_OK) rc = alloc_dev((void **)&c->fl_A, fb / 2, kWho, "accumulator");
-    if (rc != SM_OK) {
-        free_dev(c->fl_W[0]);
-        free_dev(c->fl_W[1]);
-        c->fl_W[0] = c->fl_W[1] = nullptr;
-    }
-    return rc;
+    BufGroup &b = c->fl_bufs;
+    if (!b.empty()) return SM_OK;
+    const size_t n = 2 * (size_t)c->g.V;
+    for (double2 *&W : c->fl_W) TRY(b.add(&W, n, BufKind::device, "field buffer"));
+    return b.add(&c->fl_A, n, BufKind::device, "accumulator");
 }
 
 }  // namespace
-
-namespace sm_host {
-
-void flow_free(sm_ctx *c) {
-    free_dev(c->fl_W[0]);
-    free_dev(c->fl_W[1]);
-    free_dev(c->fl_A);
-    free_dev(c->fl_series);
-    c->fl_W[0] = c->fl_W[1] = nullptr;
-    c->fl_A = nullptr;
-    c->fl_series = nullptr;
-    c->fl_points = 0;
-}
-
-}  // namespace sm_host
 
 extern "C" {
 
@@ -180,7 +157,7 @@ int sm_wilson_flow(sm_ctx *c, const sm_flow_params *p, sm_topo *series, double *
     TRY(check_ready(c));
     HIP_TRY(hipSetDevice(c->device));
     if (p->nsteps > 0) TRY(flow_buffers_ready(c));
-    TRY(series_ready(c, &c->fl_series, &c->fl_points, 1, points));
+    TRY(series_ready(c, c->fl_series_bufs, &c->fl_series, &c->fl_points, 1, points));
     const FlowFields f{false, 1, c->U, {c->fl_W[0], c->fl_W[1]}, c->fl_A, c->partials, c->fl_series};
     const double2 *last = nullptr;
     TRY(enqueue_flow(c, f, p, points, &last));
@@ -198,7 +175,7 @@ int sm_ens_topology(sm_ens *e, sm_topo *out) {
     TRY(all_have(e));
     sm_ctx *c = e->c;
     HIP_TRY(hipSetDevice(c->device));
-    TRY(series_ready(c, &e->fl_series, &e->fl_points, e->R, 1));
+    TRY(series_ready(c, e->fl_series_bufs, &e->fl_series, &e->fl_points, e->R, 1));
     launch_ens_topo(c->stream, c->g, e->R, e->U, e->part);
     launch_topo_sums(c->stream, c->g, e->R, e->part, e->fl_series, 3);
     HIP_TRY(hipGetLastError());
@@ -216,7 +193,7 @@ int sm_ens_wilson_flow(sm_ens *e, const sm_flow_params *p, sm_topo *series, doub
     TRY(all_have(e));
     sm_ctx *c = e->c;
     HIP_TRY(hipSetDevice(c->device));
-    TRY(series_ready(c, &e->fl_series, &e->fl_points, e->R, points));
+    TRY(series_ready(c, e->fl_series_bufs, &e->fl_series, &e->fl_points, e->R, points));
     const FlowFields f{true, e->R, e->U, {e->Ubak, e->chi}, e->P, e->part, e->fl_series};
     const double2 *last = nullptr;
     TRY(enqueue_flow(c, f, p, points, &last));

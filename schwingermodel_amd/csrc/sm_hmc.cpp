@@ -56,25 +56,23 @@ int sm_gather_gauge(sm_ctx *c, double *U0, double *U1) {
     if (P == 1) return download_plane_pair(c, c->U, U0, U1);
     if (c->hosted) return fail(SM_ERR_STATE, "sm_gather_gauge needs the RCCL transport");
     const size_t cnt = (size_t)4 * V;  // doubles per shard: two planes of V complex
-    double2 *buf = nullptr;
+    double *buf = nullptr;
+    BufGroup bufs("sm_gather_gauge");  // frees buf on every way out (hipFree waits for work still queued on it)
     if (c->shard == 0) {
-        HIP_TRY(hipMalloc(&buf, sizeof(double) * cnt * P));
+        TRY(bufs.add(&buf, cnt * P, BufKind::device, "gathered fields"));
         HIP_TRY(hipMemcpyAsync(buf, c->U, sizeof(double) * cnt, hipMemcpyDeviceToDevice, c->stream));
     }
     {
-        const int rc = rccl_gather_to0(c, c->stream, (const double *)c->U, (double *)buf, cnt);
+        const int rc = rccl_gather_to0(c, c->stream, (const double *)c->U, buf, cnt);
         if (rc != SM_OK) {
             (void)hipStreamSynchronize(c->stream);
-            if (buf) (void)hipFree(buf);
             return rc;
         }
     }
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (c->shard == 0) {
         std::vector<double> h(cnt * P);
-        const hipError_t e = hipMemcpy(h.data(), buf, sizeof(double) * cnt * P, hipMemcpyDeviceToHost);
-        (void)hipFree(buf);
-        HIP_TRY(e);
+        HIP_TRY(hipMemcpy(h.data(), buf, sizeof(double) * cnt * P, hipMemcpyDeviceToHost));
         // shard r holds global t in [r*Wt, (r+1)*Wt): local n = x*Wt + t
         for (int r = 0; r < P; r++) {
             const double *b = h.data() + cnt * r;

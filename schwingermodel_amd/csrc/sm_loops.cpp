@@ -37,18 +37,6 @@
 
 using namespace sm;
 
-namespace sm_host {
-
-void loops_free(sm_ctx *c) {
-    free_dev(c->lp_sk);
-    free_dev(c->lp_out);
-    c->lp_sk = nullptr;
-    c->lp_out = nullptr;
-    c->lp_cols = 0;
-}
-
-}  // namespace sm_host
-
 using namespace sm_host;
 
 namespace {
@@ -77,6 +65,20 @@ int upload_noise_ids(hipStream_t s, uint64_t *sk, int K, const uint64_t *seed, c
     return SM_OK;
 }
 
+// The (seed, k) arrays from the first call on; the loops of `cols` columns (`doubles` in all), kept while
+// they fit, regrown else. A context's or an ensemble's.
+int loops_ready(hipStream_t s, BufGroup &sk_bufs, uint64_t **sk, BufGroup &out_bufs, double **out, size_t *have,
+                size_t cols, size_t doubles) {
+    if (sk_bufs.empty()) TRY(sk_bufs.add(sk, 2 * (size_t)kBatchMax, BufKind::device, "noise seeds"));
+    if (*have >= cols) return SM_OK;
+    HIP_TRY(hipStreamSynchronize(s));
+    out_bufs.release();
+    *have = 0;
+    TRY(out_bufs.add(out, doubles, BufKind::device, "loops"));
+    *have = cols;
+    return SM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -95,16 +97,8 @@ int sm_quark_loops(sm_ctx *c, double m0, double tol, int max_iter, int solver, i
     hipStream_t s = c->stream;
     if (solver == 1) TRY(pion_eo_ready(c, Kmax));
     else TRY(batch_staging_ready(c, Kmax));
-    if (!c->lp_sk) TRY(alloc_dev((void **)&c->lp_sk, sizeof(uint64_t) * 2 * kBatchMax, kLoopsWho, "noise seeds"));
-    if (c->lp_cols < (size_t)nnoise) {
-        HIP_TRY(hipStreamSynchronize(s));
-        free_dev(c->lp_out);
-        c->lp_out = nullptr;
-        c->lp_cols = 0;
-        TRY(alloc_dev((void **)&c->lp_out, sizeof(double) * sm_loops_host::loops_doubles(1, nnoise, Nt), kLoopsWho,
-                      "loops"));
-        c->lp_cols = (size_t)nnoise;
-    }
+    TRY(loops_ready(s, c->lp_sk_bufs, &c->lp_sk, c->lp_out_bufs, &c->lp_out, &c->lp_cols, (size_t)nnoise,
+                    sm_loops_host::loops_doubles(1, nnoise, Nt)));
     const LoopNoise nz{c->lp_sk, c->lp_sk + kBatchMax};
     const BatchLinks L = shared_links(c->U, m0 + 2);
     double2 *Ue = c->eob_U, *Uo = c->eob_U + g.V;
@@ -157,16 +151,8 @@ int sm_ens_quark_loops(sm_ens *e, const double *m0, double tol, int max_iter, in
     const int R = e->R, Nt = g.Wt;
     hipStream_t s = c->stream;
     if (solver == 1) TRY(eo_fields_ready(e));
-    if (!e->lp_sk) TRY(ens_alloc((void **)&e->lp_sk, sizeof(uint64_t) * 2 * kBatchMax, "noise seeds"));
-    const size_t cols = (size_t)R * (size_t)nnoise;
-    if (e->lp_cols < cols) {
-        HIP_TRY(hipStreamSynchronize(s));
-        if (e->lp_out) (void)hipFree(e->lp_out);
-        e->lp_out = nullptr;
-        e->lp_cols = 0;
-        TRY(ens_alloc((void **)&e->lp_out, sizeof(double) * sm_loops_host::loops_doubles(R, nnoise, Nt), "loops"));
-        e->lp_cols = cols;
-    }
+    TRY(loops_ready(s, e->lp_sk_bufs, &e->lp_sk, e->lp_out_bufs, &e->lp_out, &e->lp_cols, (size_t)R * (size_t)nnoise,
+                    sm_loops_host::loops_doubles(R, nnoise, Nt)));
     for (int r = 0; r < R; ++r) e->h_mass[r] = m0[r] + 2;
     HIP_TRY(hipMemcpyAsync(e->massv, e->h_mass, sizeof(double) * (size_t)R, hipMemcpyHostToDevice, s));
     const LoopNoise nz{e->lp_sk, e->lp_sk + kBatchMax};

@@ -22,11 +22,12 @@ using namespace sm_host;
 namespace {
 
 int ensure_md(sm_ctx *c) {
-    if (c->U_alt) return SM_OK;
-    const size_t fb = sizeof(double2) * 2 * (size_t)c->g.V, rb = sizeof(double) * 2 * (size_t)c->g.V;
-    HIP_TRY(hipMalloc(&c->U_alt, fb));
-    HIP_TRY(hipMalloc(&c->Pmd, rb));
-    HIP_TRY(hipMalloc(&c->Fmd, rb));
+    BufGroup &b = c->md_bufs;
+    if (!b.empty()) return SM_OK;
+    const size_t n = 2 * (size_t)c->g.V;
+    TRY(b.add(&c->U_alt, n, BufKind::device, "second gauge field"));
+    TRY(b.add(&c->Pmd, n, BufKind::device, "momenta"));
+    TRY(b.add(&c->Fmd, n, BufKind::device, "forces"));
     return SM_OK;
 }
 

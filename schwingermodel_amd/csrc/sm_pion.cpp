@@ -70,19 +70,13 @@ int pion_eo_propagators(sm_ctx *c, const BatchWs &w, int K, const PionCols &src,
     return eo_propagators(c, w, K, eh, l, tol, max_iter, res, S);
 }
 
-void pion_free(sm_ctx *c) {
-    free_dev(c->pn_buf);
-    c->pn_buf = nullptr;
-    c->pn_K = 0;
-}
-
 int pion_eo_ready(sm_ctx *c, int K) {
     TRY(eob_ready(c, K));
     if (c->pn_K < K) {
         HIP_TRY(hipStreamSynchronize(c->stream));
-        pion_free(c);
-        TRY(alloc_dev((void **)&c->pn_buf, sizeof(double2) * 7 * (size_t)c->g.V * (size_t)K, kEoBatchWho,
-                      "pion correlator fields"));
+        c->pn_bufs.release();
+        c->pn_K = 0;
+        TRY(c->pn_bufs.add(&c->pn_buf, 7 * (size_t)c->g.V * (size_t)K, BufKind::device, "pion correlator fields"));
         c->pn_K = K;
     }
     return SM_OK;
@@ -151,9 +145,10 @@ int sm_ens_pion_correlator(sm_ens *e, const double *m0, double tol, int max_iter
     HIP_TRY(hipSetDevice(c->device));
     const int R = e->R, Nt = g.Wt;
     if (solver == 1) TRY(eo_fields_ready(e));
-    if (!e->pn_src) TRY(ens_alloc((void **)&e->pn_src, sizeof(int) * kBatchMax, "source coordinates"));
-    if (!e->pn_C)
-        TRY(ens_alloc((void **)&e->pn_C, sizeof(double) * (size_t)R * (kBatchMax / 2) * (size_t)Nt, "correlators"));
+    if (BufGroup &b = e->pn_bufs; b.empty()) {
+        TRY(b.add(&e->pn_src, (size_t)kBatchMax, BufKind::device, "source coordinates"));
+        TRY(b.add(&e->pn_C, (size_t)R * (kBatchMax / 2) * (size_t)Nt, BufKind::device, "correlators"));
+    }
     hipStream_t s = c->stream;
     int *sx = e->pn_src, *st = e->pn_src + kBatchMax / 2;
     for (int r = 0; r < R; ++r) e->h_mass[r] = m0[r] + 2;

@@ -225,6 +225,56 @@ def test_placement_buffer_names():
     assert lib.sm_placement_buffer_name(-1) is None
 
 
+def test_buf_host_check(tmp_path):
+    """BufGroup (csrc/sm_buf.h), the owner of every lazily allocated workspace, on
+    fake raw calls under the host sanitizers (tools/buf_host_check.cpp): a failure
+    injected at every request of a set frees exactly what was allocated, each by
+    its own kind, nulls every slot, names who / what / bytes, and the next build
+    succeeds in the original order; release() is idempotent; a regrow frees the
+    old set first. No GPU test reaches these paths without exhausting a card."""
+    exe = str(tmp_path / "buf_host_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    os.path.join(REPO, "tools", "buf_host_check.cpp"), "-o", exe], check=True)
+    p = subprocess.run([exe], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    assert p.stdout.strip() == "buf_host_check ok"
+
+
+def _function_lines(lines, name):
+    """0-based line numbers of the body of the function `name` defined at column 0."""
+    starts = [i for i, ln in enumerate(lines) if re.match(rf"^[A-Za-z_][\w \*:]*\b{name}\(", ln) and not ln.rstrip().endswith(";")]
+    assert len(starts) == 1, (name, starts)
+    end = next(i for i in range(starts[0], len(lines)) if lines[i].rstrip() == "}")
+    return set(range(starts[0], end + 1))
+
+
+def test_raw_allocation_calls_only_where_they_belong():
+    """hipMalloc / hipHostMalloc / hipFree / hipHostFree are called only by
+    BufGroup's raw calls, by create_common / sm_destroy (the creation-time
+    buffers) and by sm_place.cpp; the helpers BufGroup replaced are gone."""
+    csrc = os.path.join(REPO, "schwingermodel_amd", "csrc")
+    calls = re.compile(r"\b(hipMalloc|hipHostMalloc|hipFree|hipHostFree)\(")
+    gone = re.compile(r"\b(alloc_dev|free_dev|ens_alloc)\b")
+    names = sorted(os.listdir(csrc))
+    assert "sm_buf.h" in names and "sm_capi.cpp" in names and "sm_place.cpp" in names
+    seen = 0
+    for name in names:
+        with open(os.path.join(csrc, name)) as f:
+            lines = f.read().split("\n")
+        allowed = set()
+        if name == "sm_place.cpp":
+            allowed = set(range(len(lines)))
+        elif name == "sm_capi.cpp":
+            for fn in ("buf_raw_alloc", "buf_raw_free", "create_common", "sm_destroy"):
+                allowed |= _function_lines(lines, fn)
+        for i, ln in enumerate(lines):
+            assert not gone.search(ln), f"{name}:{i + 1}: {ln.strip()}"
+            if calls.search(ln):
+                seen += 1
+                assert i in allowed, f"{name}:{i + 1}: {ln.strip()}"
+    assert seen >= 20  # the creation-time buffers alone: the scan does see the calls
+
+
 def test_comm_info_null_context():
     """sm_comm_info refuses a null context and writes nothing (no GPU needed)."""
     t, n, r = ctypes.c_int(-7), ctypes.c_int(-7), ctypes.c_int(-7)
